@@ -14,6 +14,24 @@ M amortises the per-step weight stream); after --warmup untimed steps, EXACTLY
 --steps steps are timed between barrier+synchronize fences; the slowest
 rank's wall time is used. value = N_ranks × batch × steps ÷ max_elapsed.
 
+A plain run does only what the headline needs: engine set-up, admission of
+the resident batch, warmup, the timed steps, the result line. --full is the
+place for everything else the benchmark may measure (extra precisions,
+sweeps, reference comparisons); nothing lives there yet, so it currently
+runs the same path.
+
+--dump-outputs DIR writes what the LAST timed step computed as float
+.npy files (inputs are seeded, so two builds run with the same arguments can
+be compared output for output):
+  tokens.npy         [batch] token id each request received from that step,
+                     in request order
+  last_hidden.npy    [rows, hidden] final-norm hidden states the step's
+                     hipGraph replay produced (graph decode path only)
+  logits_sample.npy  [rows, cols] logits of those rows at a fixed seeded
+                     sample of vocabulary columns (graph decode path only)
+Rows are all requests in request order, or a fixed seeded sample of 512 of
+them for larger batches. Ranks other than 0 add a `.rankN` suffix.
+
 Launch (multi-GPU, by the driver):
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
       --master-addr 127.0.0.1 bench.py --gpus N --steps K --warmup W
@@ -26,6 +44,51 @@ import json
 import os
 import sys
 import time
+
+
+_DUMP_MAX_ROWS = 512
+_DUMP_MAX_COLS = 4096
+
+
+def dump_outputs(out_dir, engine, last_outputs, batch, req_prefix, rank) -> None:
+    """Write the last timed step's results under out_dir (see module doc)."""
+    import numpy as np
+    import torch
+
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = "" if rank == 0 else f".rank{rank}"
+
+    def save(name, arr):
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), arr)
+
+    # step row -> request index (the step returns rows in scheduler order)
+    req_of_row = [int(o.request_id[len(req_prefix):]) for o in last_outputs]
+    tokens = np.full(batch, -1.0, dtype=np.float64)
+    for o, r in zip(last_outputs, req_of_row):
+        tokens[r] = o.new_token_ids[-1]
+    save("tokens", tokens)
+
+    runner = engine.runner
+    if not (runner.use_graphs and len(last_outputs) <= runner.graph_max_bs):
+        return
+    # Fixed sample, independent of the rank's data seed.
+    rng = np.random.default_rng(20240531)
+    row_of_req = {r: i for i, r in enumerate(req_of_row)}
+    reqs = np.arange(batch)
+    if batch > _DUMP_MAX_ROWS:
+        reqs = np.sort(rng.choice(batch, size=_DUMP_MAX_ROWS, replace=False))
+    rows = torch.tensor([row_of_req[int(r)] for r in reqs], dtype=torch.long,
+                        device=runner.out_hidden.device)
+    vocab = engine.spec.vocab_size
+    cols = np.arange(vocab)
+    if vocab > _DUMP_MAX_COLS:
+        cols = np.sort(rng.choice(vocab, size=_DUMP_MAX_COLS, replace=False))
+    with torch.no_grad():
+        hidden = runner.out_hidden[rows]
+        save("last_hidden", hidden.float().cpu().numpy())
+        logits = engine.model.compute_logits(hidden).float()
+        cols_t = torch.from_numpy(cols).to(logits.device)
+        save("logits_sample", logits[:, cols_t].cpu().numpy())
 
 
 def main() -> None:
@@ -49,6 +112,13 @@ def main() -> None:
                         "model sharded over RCCL/xGMI (BASELINE config #4, "
                         "e.g. --tp 8 --model tower-plus-72b under torchrun "
                         "--nproc-per-node 8). Default 0 = data-parallel.")
+    parser.add_argument("--full", action="store_true",
+                        help="also run the benchmark's extra measurements "
+                        "and checks (none yet; a plain run times the "
+                        "headline only)")
+    parser.add_argument("--dump-outputs", metavar="DIR", default=None,
+                        help="write the last timed step's outputs to "
+                        "DIR/<name>.npy (float32/float64)")
     args = parser.parse_args()
 
     import torch
@@ -122,9 +192,10 @@ def main() -> None:
         temperature=args.temperature, max_tokens=args.max_model_len, ignore_eos=True
     )
     req_tag = "tp" if tp_mode else str(rank)
+    req_prefix = f"bench-{req_tag}-"
     for i in range(batch):
         ids = rng.integers(0, vocab, size=prompt_len).tolist()
-        engine.add_request(f"bench-{req_tag}-{i}", prompt_token_ids=ids, params=params)
+        engine.add_request(f"{req_prefix}{i}", prompt_token_ids=ids, params=params)
 
     t_prefill = time.perf_counter()
     stalled = 0
@@ -170,12 +241,16 @@ def main() -> None:
 
     # --- timed region
     t0 = time.perf_counter()
+    last_outputs = []
     for _ in range(args.steps):
-        engine.step()
+        last_outputs = engine.step()
     if use_gpu:
         torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     barrier_sync()
+
+    if args.dump_outputs and args.steps > 0:
+        dump_outputs(args.dump_outputs, engine, last_outputs, batch, req_prefix, rank)
 
     # slowest rank defines the job time
     if distributed:

@@ -50,6 +50,33 @@ def test_bench_single_process():
 
 
 @pytest.mark.timeout(300)
+def test_bench_full_and_dump_outputs(tmp_path):
+    """--full is accepted and keeps the result line; --dump-outputs writes
+    the last timed step's tokens as a float .npy, identical from run to
+    run (seeded inputs)."""
+    import numpy as np
+
+    dumps = []
+    for name in ("a", "b"):
+        out_dir = tmp_path / name
+        proc = subprocess.run(
+            [sys.executable, "bench.py", "--full", "--steps", "3",
+             "--warmup", "1", "--dump-outputs", str(out_dir)],
+            capture_output=True, text=True, cwd=REPO, timeout=280,
+        )
+        assert proc.returncode == 0, proc.stderr[-2000:]
+        data = _last_json_line(proc.stdout)
+        assert REQUIRED_FIELDS <= set(data)
+        assert data["steps"] == 3 and data["ms_per_step"] > 0
+        tokens = np.load(out_dir / "tokens.npy")
+        assert tokens.dtype in (np.float32, np.float64)
+        assert tokens.shape == (4,)  # CPU tiny shape: batch 4
+        assert (tokens >= 0).all() and (tokens == np.round(tokens)).all()
+        dumps.append(tokens)
+    assert np.array_equal(dumps[0], dumps[1])
+
+
+@pytest.mark.timeout(300)
 def test_bench_two_ranks_gloo():
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
     proc = subprocess.run(

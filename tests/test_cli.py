@@ -22,6 +22,9 @@ from llmq_amd.core.models import Job, Result
 
 pytestmark = pytest.mark.integration
 
+# `python -m llmq_amd` children import the package from the source tree
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
 
 @pytest.fixture()
 def broker_env(monkeypatch, tmp_path):
@@ -192,7 +195,7 @@ def test_submit_stream_echoes_results(broker_env, tmp_path):
     import sys
     worker = subprocess.Popen(
         [sys.executable, "-m", "llmq_amd", "worker", "dummy", "cls", "--delay", "0"],
-        env={**os.environ, "LLMQ_BROKER_URL": broker_env},
+        env={**os.environ, "LLMQ_BROKER_URL": broker_env}, cwd=REPO,
         stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL,
     )
     try:
@@ -235,7 +238,7 @@ def test_submit_stream_with_forced_progress_keeps_stdout_clean(broker_env, tmp_p
     import sys
     worker = subprocess.Popen(
         [sys.executable, "-m", "llmq_amd", "worker", "dummy", "clp", "--delay", "0"],
-        env={**os.environ, "LLMQ_BROKER_URL": broker_env},
+        env={**os.environ, "LLMQ_BROKER_URL": broker_env}, cwd=REPO,
         stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL,
     )
     try:
