@@ -24,48 +24,51 @@ def _sources_mtime() -> float:
     return max(p.stat().st_mtime for p in (HERE / "hip").iterdir() if p.is_file())
 
 
-def build(verbose: bool = False, force: bool = False) -> Path:
-    if OUT.is_file() and not force and OUT.stat().st_mtime >= _sources_mtime():
-        return OUT
+def _compile(name: str, build_dir: Path, out: Path, extra_defines=(),
+             verbose: bool = False) -> Path:
+    """Compile the umbrella TU as extension `name` in `build_dir` and copy
+    the resulting .so to `out`."""
     # torch.utils.cpp_extension tracks only the listed sources (ops.hip), not
     # the files it #includes — touch the umbrella TU so edits to any kernel
     # file trigger a rebuild.
     SRC.touch()
-    if force:
-        shutil.rmtree(BUILD_DIR, ignore_errors=True)
     os.environ.setdefault("PYTORCH_ROCM_ARCH", "gfx950")
     os.environ.setdefault("MAX_JOBS", "8")
     from torch.utils.cpp_extension import load
 
-    BUILD_DIR.mkdir(exist_ok=True)
+    build_dir.mkdir(exist_ok=True)
+    flags = ["-O3", "-std=c++20", *extra_defines]
+    load(
+        name=name,
+        sources=[str(SRC)],
+        extra_cflags=flags,
+        extra_cuda_cflags=flags,
+        build_directory=str(build_dir),
+        is_python_module=False,
+        verbose=verbose,
+    )
+    built = build_dir / f"{name}.so"
+    if not built.is_file():
+        candidates = list(build_dir.glob("*.so"))
+        if not candidates:
+            raise RuntimeError(f"build produced no .so under {build_dir}")
+        built = candidates[0]
+    shutil.copy2(built, out)
+    return out
 
-    def _load() -> None:
-        load(
-            name="llmq_amd_hip_ops",
-            sources=[str(SRC)],
-            extra_cflags=["-O3", "-std=c++20"],
-            extra_cuda_cflags=["-O3", "-std=c++20"],
-            build_directory=str(BUILD_DIR),
-            is_python_module=False,
-            verbose=verbose,
-        )
 
+def build(verbose: bool = False, force: bool = False) -> Path:
+    if OUT.is_file() and not force and OUT.stat().st_mtime >= _sources_mtime():
+        return OUT
+    if force:
+        shutil.rmtree(BUILD_DIR, ignore_errors=True)
     try:
-        _load()
+        return _compile("llmq_amd_hip_ops", BUILD_DIR, OUT, verbose=verbose)
     except Exception:
         # A stale incremental object (e.g. after a template-signature change)
         # can link a .so with dangling device stubs — rebuild clean once.
         shutil.rmtree(BUILD_DIR, ignore_errors=True)
-        BUILD_DIR.mkdir(exist_ok=True)
-        _load()
-    built = BUILD_DIR / "llmq_amd_hip_ops.so"
-    if not built.is_file():
-        candidates = list(BUILD_DIR.glob("*.so"))
-        if not candidates:
-            raise RuntimeError(f"build produced no .so under {BUILD_DIR}")
-        built = candidates[0]
-    shutil.copy2(built, OUT)
-    return OUT
+        return _compile("llmq_amd_hip_ops", BUILD_DIR, OUT, verbose=verbose)
 
 
 def build_ab_defer_on(verbose: bool = False) -> Path:
@@ -76,26 +79,10 @@ def build_ab_defer_on(verbose: bool = False) -> Path:
     out = HERE / "_ab_defer_on.so"
     if out.is_file() and out.stat().st_mtime >= _sources_mtime():
         return out
-    SRC.touch()
-    os.environ.setdefault("PYTORCH_ROCM_ARCH", "gfx950")
-    os.environ.setdefault("MAX_JOBS", "8")
-    from torch.utils.cpp_extension import load
-
     bdir = HERE / "build_ab"
     shutil.rmtree(bdir, ignore_errors=True)
-    bdir.mkdir(exist_ok=True)
-    load(
-        name="llmq_amd_hip_ops_ab",
-        sources=[str(SRC)],
-        extra_cflags=["-O3", "-std=c++20", "-DLLMQ_DEFER_ON"],
-        extra_cuda_cflags=["-O3", "-std=c++20", "-DLLMQ_DEFER_ON"],
-        build_directory=str(bdir),
-        is_python_module=False,
-        verbose=verbose,
-    )
-    built = next(bdir.glob("*.so"))
-    shutil.copy2(built, out)
-    return out
+    return _compile("llmq_amd_hip_ops_ab", bdir, out, ["-DLLMQ_DEFER_ON"],
+                    verbose=verbose)
 
 
 if __name__ == "__main__":

@@ -38,6 +38,26 @@ void dispatch_dtype(const at::Tensor& t, const char* name, F&& f) {
   }
 }
 
+// Calls f.template operator()<HD>() for the compile-time HD equal to D.
+template <int... HDs, typename F>
+void dispatch_head_dim(int D, F&& f) {
+  const bool hit =
+      ((D == HDs ? (f.template operator()<HDs>(), true) : false) || ...);
+  TORCH_CHECK(hit, "unsupported head_dim ", D);
+}
+
+// KV-cache element type for activations T: T itself, or fp8 (bf16 only).
+template <typename T, typename F>
+void dispatch_cache_type(bool fp8_cache, F&& f) {
+  if (!fp8_cache) {
+    f.template operator()<T>();
+  } else if constexpr (std::is_same_v<T, __hip_bfloat16>) {
+    f.template operator()<__hip_fp8_e4m3>();
+  } else {
+    TORCH_CHECK(false, "fp8 KV cache requires bf16 activations");
+  }
+}
+
 // ---------------------------------------------------------------- norms --
 
 void rmsnorm(at::Tensor out, at::Tensor in, at::Tensor weight, double eps,
@@ -144,28 +164,15 @@ void reshape_and_cache(at::Tensor key, at::Tensor value, at::Tensor k_cache,
   TORCH_CHECK(slot_mapping.scalar_type() == at::kLong);
   const bool fp8_cache = k_cache.scalar_type() == at::kFloat8_e4m3fn;
   dispatch_dtype(key, "reshape_and_cache", [&]<typename T>() {
-    if (fp8_cache) {
-      if constexpr (std::is_same_v<T, __hip_bfloat16>) {
-        hipLaunchKernelGGL((reshape_and_cache_kernel<T, __hip_fp8_e4m3>),
-                           dim3(T_), dim3(128), 0, stream(),
-                           reinterpret_cast<const T*>(key.data_ptr()),
-                           reinterpret_cast<const T*>(value.data_ptr()),
-                           reinterpret_cast<__hip_fp8_e4m3*>(k_cache.data_ptr()),
-                           reinterpret_cast<__hip_fp8_e4m3*>(v_cache.data_ptr()),
-                           slot_mapping.data_ptr<long>(), kvh, d, bs,
-                           key.stride(0), value.stride(0));
-      } else {
-        TORCH_CHECK(false, "fp8 KV cache requires bf16 activations");
-      }
-      return;
-    }
-    hipLaunchKernelGGL(reshape_and_cache_kernel<T>, dim3(T_), dim3(128), 0,
-                       stream(), reinterpret_cast<const T*>(key.data_ptr()),
-                       reinterpret_cast<const T*>(value.data_ptr()),
-                       reinterpret_cast<T*>(k_cache.data_ptr()),
-                       reinterpret_cast<T*>(v_cache.data_ptr()),
-                       slot_mapping.data_ptr<long>(), kvh, d, bs,
-                       key.stride(0), value.stride(0));
+    dispatch_cache_type<T>(fp8_cache, [&]<typename TC>() {
+      hipLaunchKernelGGL((reshape_and_cache_kernel<T, TC>), dim3(T_), dim3(128),
+                         0, stream(), reinterpret_cast<const T*>(key.data_ptr()),
+                         reinterpret_cast<const T*>(value.data_ptr()),
+                         reinterpret_cast<TC*>(k_cache.data_ptr()),
+                         reinterpret_cast<TC*>(v_cache.data_ptr()),
+                         slot_mapping.data_ptr<long>(), kvh, d, bs,
+                         key.stride(0), value.stride(0));
+    });
   });
 }
 
@@ -186,32 +193,17 @@ void rope_and_cache(at::Tensor q, at::Tensor k, at::Tensor value,
   TORCH_CHECK(q.stride(1) == d && k.stride(1) == d, "head dim must be packed");
   const bool fp8_cache = k_cache.scalar_type() == at::kFloat8_e4m3fn;
   dispatch_dtype(q, "rope_and_cache", [&]<typename T>() {
-    if (fp8_cache) {
-      if constexpr (std::is_same_v<T, __hip_bfloat16>) {
-        hipLaunchKernelGGL((rope_and_cache_kernel<T, __hip_fp8_e4m3>),
-                           dim3(T_), dim3(256), 0, stream(),
-                           reinterpret_cast<T*>(q.data_ptr()),
-                           reinterpret_cast<T*>(k.data_ptr()),
-                           reinterpret_cast<const T*>(value.data_ptr()),
-                           reinterpret_cast<__hip_fp8_e4m3*>(k_cache.data_ptr()),
-                           reinterpret_cast<__hip_fp8_e4m3*>(v_cache.data_ptr()),
-                           positions.data_ptr<long>(), cos_sin.data_ptr<float>(),
-                           slot_mapping.data_ptr<long>(), hq, hk, d, bs,
-                           q.stride(0), k.stride(0), value.stride(0));
-      } else {
-        TORCH_CHECK(false, "fp8 KV cache requires bf16 activations");
-      }
-      return;
-    }
-    hipLaunchKernelGGL(rope_and_cache_kernel<T>, dim3(T_), dim3(256), 0,
-                       stream(), reinterpret_cast<T*>(q.data_ptr()),
-                       reinterpret_cast<T*>(k.data_ptr()),
-                       reinterpret_cast<const T*>(value.data_ptr()),
-                       reinterpret_cast<T*>(k_cache.data_ptr()),
-                       reinterpret_cast<T*>(v_cache.data_ptr()),
-                       positions.data_ptr<long>(), cos_sin.data_ptr<float>(),
-                       slot_mapping.data_ptr<long>(), hq, hk, d, bs,
-                       q.stride(0), k.stride(0), value.stride(0));
+    dispatch_cache_type<T>(fp8_cache, [&]<typename TC>() {
+      hipLaunchKernelGGL((rope_and_cache_kernel<T, TC>), dim3(T_), dim3(256), 0,
+                         stream(), reinterpret_cast<T*>(q.data_ptr()),
+                         reinterpret_cast<T*>(k.data_ptr()),
+                         reinterpret_cast<const T*>(value.data_ptr()),
+                         reinterpret_cast<TC*>(k_cache.data_ptr()),
+                         reinterpret_cast<TC*>(v_cache.data_ptr()),
+                         positions.data_ptr<long>(), cos_sin.data_ptr<float>(),
+                         slot_mapping.data_ptr<long>(), hq, hk, d, bs,
+                         q.stride(0), k.stride(0), value.stride(0));
+    });
   });
 }
 
@@ -230,16 +222,12 @@ void launch_decode(at::Tensor& out, const at::Tensor& q, const at::Tensor& kc,
   TORCH_CHECK(H % KVH == 0, "num_heads must divide num_kv_heads");
   TORCH_CHECK(bs == 16 || bs == 32, "block_size must be 16 or 32");
   dim3 grid(B, KVH);
-  // bf16 + MFMA-supported head dims → matrix-core kernel (G padded to 16).
-  // NW = waves per workgroup (keys-per-chunk = 16·NW); 8 halves the
-  // barriers per token vs 4 at the same waves/SIMD (A/B-able via
-  // LLMQ_DECODE_NW).
+  // bf16 + MFMA-supported head dims → matrix-core kernels (G padded to 16),
+  // 8 waves per workgroup.
   if constexpr (std::is_same_v<T, __hip_bfloat16>) {
     if ((D == 128 || D == 256) && G <= 16) {
-      static const int nw_env = [] {
-        const char* e = getenv("LLMQ_DECODE_NW");
-        return e ? atoi(e) : 8;
-      }();
+      using BF = __hip_bfloat16;
+      using F8 = __hip_fp8_e4m3;
       // Split-KV: when B×KVH under-fills the chip (TP ranks hold few kv
       // heads; small batches), split the context across z-workgroups and
       // merge fp32 partials. Target ≥512 workgroups (2 resident per CU).
@@ -253,95 +241,15 @@ void launch_decode(at::Tensor& out, const at::Tensor& q, const at::Tensor& kc,
         scratch_ptr = scratch.data_ptr<float>();
       }
       dim3 sgrid(B, KVH, nsplit);
-      const bool fp8_cache = kc.scalar_type() == at::kFloat8_e4m3fn;
-      // Software-pipelined glds kernel (default): LLMQ_DECODE_PIPE selects
-      // the chunk size (64 | 128 keys) or 0 = the plain-staged kernel.
-      // Read per call so microbenches can A/B in-process. Preconditions:
-      // bf16 cache (glds cannot convert fp8 during the LDS write) and the
-      // whole block table staged in LDS (no per-granule LDS-vs-global
-      // select — guide §5 trap 4c).
-      const char* pe = getenv("LLMQ_DECODE_PIPE");
-      const int pipe_kt = pe ? atoi(pe) : 64;
-      if (fp8_cache && pipe_kt > 0 && max_blocks <= PD_MAX_BT) {
-        // fp8 glds pipeline: raw-fp8 staging + native packed cvt VOPs
-        auto lf8 = [&]<int HD>() {
-          hipLaunchKernelGGL((paged_decode_pipe_fp8_kernel<HD, 8>), sgrid,
-                             dim3(8 * 64), 0, stream(),
-                             reinterpret_cast<__hip_bfloat16*>(out.data_ptr()),
-                             reinterpret_cast<const __hip_bfloat16*>(q.data_ptr()),
-                             reinterpret_cast<const __hip_fp8_e4m3*>(kc.data_ptr()),
-                             reinterpret_cast<const __hip_fp8_e4m3*>(vc.data_ptr()),
-                             bt.data_ptr<int>(), cl.data_ptr<int>(), scratch_ptr,
-                             H, KVH, bs, max_blocks, (float)scale,
-                             (float)softcap, (int)window, q.stride(0),
-                             out.stride(0));
-          if (nsplit > 1) {
-            hipLaunchKernelGGL((decode_splitkv_merge_kernel<HD>),
-                               dim3(B, KVH, G), dim3(64), 0, stream(),
-                               reinterpret_cast<__hip_bfloat16*>(out.data_ptr()),
-                               scratch_ptr, KVH, G, nsplit, out.stride(0));
-          }
-        };
-        if (D == 128) lf8.template operator()<128>();
-        else lf8.template operator()<256>();
-        return;
-      }
-      if (!fp8_cache && pipe_kt > 0 && max_blocks <= PD_MAX_BT) {
-        auto lp = [&]<int HD, int KT>() {
-          hipLaunchKernelGGL((paged_decode_pipe_kernel<HD, 8, KT>), sgrid,
-                             dim3(8 * 64), 0, stream(),
-                             reinterpret_cast<__hip_bfloat16*>(out.data_ptr()),
-                             reinterpret_cast<const __hip_bfloat16*>(q.data_ptr()),
-                             reinterpret_cast<const __hip_bfloat16*>(kc.data_ptr()),
-                             reinterpret_cast<const __hip_bfloat16*>(vc.data_ptr()),
-                             bt.data_ptr<int>(), cl.data_ptr<int>(), scratch_ptr,
-                             H, KVH, bs, max_blocks, (float)scale,
-                             (float)softcap, (int)window, q.stride(0),
-                             out.stride(0));
-          if (nsplit > 1) {
-            hipLaunchKernelGGL((decode_splitkv_merge_kernel<HD>),
-                               dim3(B, KVH, G), dim3(64), 0, stream(),
-                               reinterpret_cast<__hip_bfloat16*>(out.data_ptr()),
-                               scratch_ptr, KVH, G, nsplit, out.stride(0));
-          }
-        };
-        if (pipe_kt == 32) {  // ring variant: separate K/V slots, 32-key
-          auto lr = [&]<int HD>() {
-            hipLaunchKernelGGL((paged_decode_ring_kernel<HD, 8>), sgrid,
-                               dim3(8 * 64), 0, stream(),
-                               reinterpret_cast<__hip_bfloat16*>(out.data_ptr()),
-                               reinterpret_cast<const __hip_bfloat16*>(q.data_ptr()),
-                               reinterpret_cast<const __hip_bfloat16*>(kc.data_ptr()),
-                               reinterpret_cast<const __hip_bfloat16*>(vc.data_ptr()),
-                               bt.data_ptr<int>(), cl.data_ptr<int>(), scratch_ptr,
-                               H, KVH, bs, max_blocks, (float)scale,
-                               (float)softcap, (int)window, q.stride(0),
-                               out.stride(0));
-            if (nsplit > 1) {
-              hipLaunchKernelGGL((decode_splitkv_merge_kernel<HD>),
-                                 dim3(B, KVH, G), dim3(64), 0, stream(),
-                                 reinterpret_cast<__hip_bfloat16*>(out.data_ptr()),
-                                 scratch_ptr, KVH, G, nsplit, out.stride(0));
-            }
-          };
-          if (D == 128) lr.template operator()<128>();
-          else lr.template operator()<256>();
-          return;
-        }
-        if (D == 128) {
-          if (pipe_kt >= 128) lp.template operator()<128, 128>();
-          else lp.template operator()<128, 64>();
-        } else {
-          if (pipe_kt >= 128) lp.template operator()<256, 128>();
-          else lp.template operator()<256, 64>();
-        }
-        return;
-      }
-      auto lm = [&]<int HD, int NW, typename TC>() {
-        hipLaunchKernelGGL((paged_decode_mfma_kernel<HD, NW, TC>), sgrid,
-                           dim3(NW * 64), 0, stream(),
-                           reinterpret_cast<__hip_bfloat16*>(out.data_ptr()),
-                           reinterpret_cast<const __hip_bfloat16*>(q.data_ptr()),
+      // One launch for the whole MFMA family (one parameter list up to the
+      // cache element type TC), then the split-KV merge if the context
+      // was split.
+      auto launch = [&]<int HD, typename TC>(void (*kernel)(
+          BF*, const BF*, const TC*, const TC*, const int*, const int*, float*,
+          int, int, int, int, float, float, int, long, long)) {
+        hipLaunchKernelGGL(kernel, sgrid, dim3(8 * 64), 0, stream(),
+                           reinterpret_cast<BF*>(out.data_ptr()),
+                           reinterpret_cast<const BF*>(q.data_ptr()),
                            reinterpret_cast<const TC*>(kc.data_ptr()),
                            reinterpret_cast<const TC*>(vc.data_ptr()),
                            bt.data_ptr<int>(), cl.data_ptr<int>(), scratch_ptr,
@@ -351,26 +259,34 @@ void launch_decode(at::Tensor& out, const at::Tensor& q, const at::Tensor& kc,
         if (nsplit > 1) {
           hipLaunchKernelGGL((decode_splitkv_merge_kernel<HD>),
                              dim3(B, KVH, G), dim3(64), 0, stream(),
-                             reinterpret_cast<__hip_bfloat16*>(out.data_ptr()),
+                             reinterpret_cast<BF*>(out.data_ptr()),
                              scratch_ptr, KVH, G, nsplit, out.stride(0));
         }
       };
-      using BF = __hip_bfloat16;
-      using F8 = __hip_fp8_e4m3;
-      if (fp8_cache) {  // fp8 KV rides the default NW=8 configuration
-        if (D == 128) lm.template operator()<128, 8, F8>();
-        else lm.template operator()<256, 8, F8>();
-      } else if (D == 128) {
-        // NW=16 needs D/NW >= 16 (a full MFMA dim tile per wave)
-        if (nw_env == 2) lm.template operator()<128, 2, BF>();
-        else if (nw_env == 4) lm.template operator()<128, 4, BF>();
-        else lm.template operator()<128, 8, BF>();
-      } else {
-        if (nw_env == 2) lm.template operator()<256, 2, BF>();
-        else if (nw_env == 4) lm.template operator()<256, 4, BF>();
-        else if (nw_env == 16) lm.template operator()<256, 16, BF>();
-        else lm.template operator()<256, 8, BF>();
-      }
+      const bool fp8_cache = kc.scalar_type() == at::kFloat8_e4m3fn;
+      // Software-pipelined glds kernels (default): LLMQ_DECODE_PIPE selects
+      // the bf16 chunk size (>= 128 → 128 keys, else 64) or 0 = the
+      // plain-staged kernel. Read per call so microbenches can A/B
+      // in-process. Precondition: the whole block table staged in LDS (no
+      // per-granule LDS-vs-global select — guide §5 trap 4c). fp8 caches
+      // have their own pipe kernel (raw-fp8 staging + native packed cvt
+      // VOPs: glds cannot convert during the LDS write).
+      const char* pe = getenv("LLMQ_DECODE_PIPE");
+      const int pipe_kt = pe ? atoi(pe) : 64;
+      const bool pipe = pipe_kt > 0 && max_blocks <= PD_MAX_BT;
+      dispatch_head_dim<128, 256>(D, [&]<int HD>() {
+        if (fp8_cache) {
+          launch.template operator()<HD, F8>(
+              pipe ? paged_decode_pipe_fp8_kernel<HD, 8>
+                   : paged_decode_mfma_kernel<HD, 8, F8>);
+        } else if (pipe) {
+          launch.template operator()<HD, BF>(
+              pipe_kt >= 128 ? paged_decode_pipe_kernel<HD, 8, 128>
+                             : paged_decode_pipe_kernel<HD, 8, 64>);
+        } else {
+          launch.template operator()<HD, BF>(paged_decode_mfma_kernel<HD, 8, BF>);
+        }
+      });
       return;
     }
   }
@@ -383,7 +299,7 @@ void launch_decode(at::Tensor& out, const at::Tensor& q, const at::Tensor& kc,
   const int subs = 256 / (32 * G);
   const int lds = (G * D + DECODE_CHUNK * G + subs * G * (D + 2)) * sizeof(float) +
                   16 * sizeof(int);
-  auto l = [&]<int HD>() {
+  dispatch_head_dim<64, 128, 256>(D, [&]<int HD>() {
     hipLaunchKernelGGL((paged_decode_attention_kernel<T, HD>), grid, dim3(256),
                        lds, stream(), reinterpret_cast<T*>(out.data_ptr()),
                        reinterpret_cast<const T*>(q.data_ptr()),
@@ -392,13 +308,7 @@ void launch_decode(at::Tensor& out, const at::Tensor& q, const at::Tensor& kc,
                        bt.data_ptr<int>(), cl.data_ptr<int>(), H, KVH, bs,
                        max_blocks, (float)scale, (float)softcap, (int)window,
                        q.stride(0), out.stride(0));
-  };
-  switch (D) {
-    case 64: l.template operator()<64>(); break;
-    case 128: l.template operator()<128>(); break;
-    case 256: l.template operator()<256>(); break;
-    default: TORCH_CHECK(false, "unsupported head_dim ", D);
-  }
+  });
 }
 
 void paged_decode_attention(at::Tensor out, at::Tensor q, at::Tensor k_cache,
@@ -453,15 +363,11 @@ void launch_prefill(at::Tensor& out, const at::Tensor& q, const at::Tensor& k,
                          (float)scale, (float)softcap, (int)window,
                          q.stride(0), k.stride(0), v.stride(0), out.stride(0));
     };
-    switch (D) {
-      case 64: lf.template operator()<64>(); return;
-      case 128: lf.template operator()<128>(); return;
-      case 256: lf.template operator()<256>(); return;
-      default: TORCH_CHECK(false, "unsupported head_dim ", D);
-    }
+    dispatch_head_dim<64, 128, 256>(D, lf);
+    return;
   }
   dim3 grid(B, H);
-  auto l = [&]<int HD>() {
+  dispatch_head_dim<64, 128, 256>(D, [&]<int HD>() {
     hipLaunchKernelGGL((varlen_prefill_attention_kernel<T, HD>), grid,
                        dim3(256), 0, stream(),
                        reinterpret_cast<T*>(out.data_ptr()),
@@ -471,13 +377,7 @@ void launch_prefill(at::Tensor& out, const at::Tensor& q, const at::Tensor& k,
                        cu.data_ptr<int>(), cu_k.data_ptr<int>(), H, KVH,
                        (float)scale, (float)softcap, (int)window,
                        q.stride(0), k.stride(0), v.stride(0), out.stride(0));
-  };
-  switch (D) {
-    case 64: l.template operator()<64>(); break;
-    case 128: l.template operator()<128>(); break;
-    case 256: l.template operator()<256>(); break;
-    default: TORCH_CHECK(false, "unsupported head_dim ", D);
-  }
+  });
 }
 
 void varlen_prefill_attention(at::Tensor out, at::Tensor q, at::Tensor k,

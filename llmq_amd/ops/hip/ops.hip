@@ -2,7 +2,8 @@
 // (template instantiation happens at the launch sites in bindings.cpp).
 #include "elementwise.hip"
 #include "kvcache.hip"
-#include "attention.hip"
+#include "prefill_attention.hip"
+#include "decode_attention.hip"
 #include "skinny_gemm.hip"
 #include "sampling.hip"
 #include "bindings.cpp"

@@ -193,6 +193,26 @@ class TestDecodeAttention:
         )
         assert_close_to_f32_ref(out.cpu(), ref, 2e-2, 1e-1)
 
+    def test_block_table_wider_than_lds_stage(self):
+        """A block table wider than the 1024 entries the MFMA kernels stage
+        in LDS sends the default dispatch to the plain-staged kernel, whose
+        row-0 context (16,400 tokens = 1025 blocks) reads the tail entries
+        from global memory."""
+        dtype = torch.bfloat16
+        B, G, KVH, D, BS = 2, 4, 1, 128, 16
+        H = G * KVH
+        torch.manual_seed(7)
+        ctx = torch.tensor([16400, 100], dtype=torch.int32, device=DEV)
+        kc, vc, bt = _build_cache(B, KVH, D, BS, 1030 * BS, dtype)
+        assert bt.size(1) == 1030
+        q = torch.randn(B, H, D, device=DEV, dtype=dtype)
+        scale = D ** -0.5
+        out = ops.paged_decode_attention(q, kc, vc, bt, ctx, scale)
+        ref = torch_ref.paged_decode_attention(
+            q.float().cpu(), kc.float().cpu(), vc.float().cpu(), bt.cpu(), ctx.cpu(), scale
+        )
+        assert_close_to_f32_ref(out.cpu(), ref, 2e-2, 1e-1)
+
     @pytest.mark.parametrize("softcap,window", [(50.0, 0), (0.0, 64), (50.0, 64)])
     def test_softcap_window(self, softcap, window):
         dtype = torch.bfloat16
@@ -613,6 +633,34 @@ class TestFp8KVCache:
         ref = torch_ref.paged_decode_attention(
             q.float().cpu(), kc8.float().cpu(), vc8.float().cpu(),
             bt.cpu(), ctx.cpu(), scale,
+        )
+        assert_close_to_f32_ref(out.cpu(), ref, 2e-2, 1e-1)
+
+    @pytest.mark.parametrize("pipe", ["0", "64"])
+    @pytest.mark.parametrize("B,G,KVH,D,softcap,window", [
+        (9, 4, 8, 128, 0.0, 0),
+        (5, 2, 8, 256, 50.0, 100),  # softcap + window (start mid-chunk)
+        (2, 16, 1, 256, 0.0, 0),    # split-KV z-grid engaged
+    ])
+    def test_pipe_and_plain_variants(self, pipe, B, G, KVH, D, softcap, window,
+                                     monkeypatch):
+        """fp8 KV through both the fp8 glds pipeline (LLMQ_DECODE_PIPE=64) and
+        the plain-staged kernel (=0), at D=128, with softcap/window and on
+        the split-KV path, vs the fp32 reference on the DEQUANTIZED cache."""
+        monkeypatch.setenv("LLMQ_DECODE_PIPE", pipe)
+        H = G * KVH
+        torch.manual_seed(6)
+        all_ctx = [1, 63, 64, 65, 127, 128, 129, 200, 1025]
+        ctx = torch.tensor(all_ctx[-B:], dtype=torch.int32, device=DEV)
+        kc, vc, bt = _build_cache(B, KVH, D, 16, 1025, torch.bfloat16)
+        kc8 = kc.to(torch.float8_e4m3fn)
+        vc8 = vc.to(torch.float8_e4m3fn)
+        q = torch.randn(B, H, D, device=DEV, dtype=torch.bfloat16)
+        scale = D ** -0.5
+        out = ops.paged_decode_attention(q, kc8, vc8, bt, ctx, scale, softcap, window)
+        ref = torch_ref.paged_decode_attention(
+            q.float().cpu(), kc8.float().cpu(), vc8.float().cpu(),
+            bt.cpu(), ctx.cpu(), scale, softcap, window,
         )
         assert_close_to_f32_ref(out.cpu(), ref, 2e-2, 1e-1)
 
