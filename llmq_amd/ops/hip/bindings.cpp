@@ -274,18 +274,29 @@ void launch_decode(at::Tensor& out, const at::Tensor& q, const at::Tensor& kc,
       const char* pe = getenv("LLMQ_DECODE_PIPE");
       const int pipe_kt = pe ? atoi(pe) : 64;
       const bool pipe = pipe_kt > 0 && max_blocks <= PD_MAX_BT;
+      // NREG: how many of a lane's 4 softmax registers hold q-heads with
+      // the kernels' row placement (heads 4*reg .. 4*reg+3 in register reg):
+      // ceil(G/4), with 3 rounded up to 4.
+      auto dispatch_nreg = [&](auto&& f) {
+        if (G <= 4) f.template operator()<1>();
+        else if (G <= 8) f.template operator()<2>();
+        else f.template operator()<4>();
+      };
       dispatch_head_dim<128, 256>(D, [&]<int HD>() {
-        if (fp8_cache) {
-          launch.template operator()<HD, F8>(
-              pipe ? paged_decode_pipe_fp8_kernel<HD, 8>
-                   : paged_decode_mfma_kernel<HD, 8, F8>);
-        } else if (pipe) {
-          launch.template operator()<HD, BF>(
-              pipe_kt >= 128 ? paged_decode_pipe_kernel<HD, 8, 128>
-                             : paged_decode_pipe_kernel<HD, 8, 64>);
-        } else {
-          launch.template operator()<HD, BF>(paged_decode_mfma_kernel<HD, 8, BF>);
-        }
+        dispatch_nreg([&]<int NREG>() {
+          if (fp8_cache) {
+            launch.template operator()<HD, F8>(
+                pipe ? paged_decode_pipe_fp8_kernel<HD, 8, NREG>
+                     : paged_decode_mfma_kernel<HD, 8, NREG, F8>);
+          } else if (pipe) {
+            launch.template operator()<HD, BF>(
+                pipe_kt >= 128 ? paged_decode_pipe_kernel<HD, 8, 128, NREG>
+                               : paged_decode_pipe_kernel<HD, 8, 64, NREG>);
+          } else {
+            launch.template operator()<HD, BF>(
+                paged_decode_mfma_kernel<HD, 8, NREG, BF>);
+          }
+        });
       });
       return;
     }

@@ -208,8 +208,11 @@ __global__ __launch_bounds__(256) void paged_decode_attention_kernel(
 // ------------------------------------------------------- MFMA paged decode --
 // Single-token GQA decode attention on matrix cores (bf16, D in {128,256},
 // G <= 16). One workgroup per (sequence, kv_head); the GQA query group is
-// padded to a 16-row MFMA tile (pad rows repeat q-head 0 and are never
-// stored). K and V SHARE one LDS tile buffer: per 64-key chunk
+// padded to a 16-row MFMA tile: q-head g sits in tile row pd_row_head(g), so
+// the real rows fill softmax register 0 of every lane first and only
+// NREG = ceil(G/4) of a lane's 4 accumulator registers carry a q-head (pad
+// rows repeat q-head 0 and are never stored). K and V SHARE one LDS tile
+// buffer: per 64-key chunk
 //   stage K -> sync -> S = QK^T (wave w: 16-key slab, MFMA 16x16x32) ->
 //   sync -> stage V into the same buffer (its HBM latency hides under the
 //   softmax VALU work) + combine row maxes / build P / update per-wave l ->
@@ -245,12 +248,20 @@ DEVINL bf16x8_t kv8_to_bf16(const __hip_fp8_e4m3* p) {
 // coordinates throughout: col = lane & 15 (key for S, q row for OT),
 // kgrp = lane >> 4, softmax rows r = kgrp*4 + reg.
 
-// Q fragments: A-operand rows = padded GQA q rows (row = lane&15; pad rows
-// repeat q-head 0 and are never stored).
+// Tile row <-> q-head: a self-inverse 4x4 transpose of the index. Row
+// r = kgrp*4 + reg holds head reg*4 + kgrp, so heads 0..3 are register 0 of
+// kgrp 0..3, heads 4..7 register 1, ... and registers >= NREG = ceil(G/4)
+// hold pad rows only: the per-chunk softmax work (scale, softcap, row max,
+// exp, row sum) runs for reg < NREG and skips them.
+DEVINL int pd_row_head(int r) { return (r & 3) * 4 + (r >> 2); }
+
+// Q fragments: A-operand rows = padded GQA q rows (row = lane&15 holds
+// q-head pd_row_head(row); pad rows repeat q-head 0 and are never stored).
 template <int D, bool FENCE>
 DEVINL void pd_load_qfrag(bf16x8_t (&qfrag)[D / 32], const __hip_bfloat16* q,
                           int b, int kh, int G, long q_stride, int col, int kgrp) {
-  const int qrow = (col < G) ? col : 0;
+  const int g = pd_row_head(col);
+  const int qrow = (g < G) ? g : 0;
   const __hip_bfloat16* qp = q + (long)b * q_stride + (long)(kh * G + qrow) * D;
 #pragma unroll
   for (int ks = 0; ks < D / 32; ++ks) {
@@ -281,14 +292,15 @@ DEVINL void pd_chunk_range(int L, int window, int& start, int& range_lo,
 }
 
 // Scale, softcap and dead-key mask of this lane's S column (absolute key
-// `key`), then the row max over the 16 col lanes. The caller stores mx to
-// its per-slab max partials.
+// `key`), then the row max over the 16 col lanes, for the NREG registers
+// that hold q-heads. The caller stores mx to its per-slab max partials.
+template <int NREG>
 DEVINL void pd_scale_mask_rowmax(const f32x4_t& s, int key, int L, int start,
-                                 float scale, float softcap, float (&sv)[4],
-                                 float (&mx)[4]) {
+                                 float scale, float softcap, float (&sv)[NREG],
+                                 float (&mx)[NREG]) {
   const bool dead = key >= L || key < start;
 #pragma unroll
-  for (int reg = 0; reg < 4; ++reg) {
+  for (int reg = 0; reg < NREG; ++reg) {
     float x = s[reg] * scale;
     if (softcap > 0.f) x = tanhf(x / softcap) * softcap;
     sv[reg] = dead ? -1e30f : x;
@@ -299,18 +311,32 @@ DEVINL void pd_scale_mask_rowmax(const f32x4_t& s, int key, int L, int start,
   }
 }
 
-// Combine the per-slab maxes (identical on every wave), build P, update l;
-// stores alpha (wave 0) and this wave's P slab. Returns whether OT must be
-// rescaled by alpha this chunk (always, in the default build). Used by the
-// two pipe kernels; the plain kernel keeps a fused copy (see there).
-template <int SLABS, int PD_KT>
+// The chunk loop writes P rows and alpha entries of registers < NREG only;
+// the rest still feed the PV MFMA's pad columns and their `ot *= alpha`.
+// Set them once (P = 0, alpha = 1) so the kernel never multiplies
+// uninitialised LDS. Prologue only: the caller's next barrier publishes it.
+template <int NREG, int PD_KT, int NT>
+DEVINL void pd_init_pad_rows(short* p_lds, float* alpha_s, int tid) {
+  if constexpr (NREG < 4) {
+    for (int i = tid; i < 16 * PD_KT; i += NT)
+      if (((i / PD_KT) & 3) >= NREG) p_lds[i] = 0;
+    if (tid < 16 && (tid & 3) >= NREG) alpha_s[tid] = 1.f;
+  }
+}
+
+// Combine the per-slab maxes (identical on every wave that runs this), build
+// P, update l; stores alpha (wave 0) and this wave's P slab. Returns whether
+// OT must be rescaled by alpha this chunk (always, in the default build).
+// Used by the two pipe kernels; the plain kernel keeps a fused copy (see
+// there).
+template <int SLABS, int PD_KT, int NREG>
 DEVINL bool pd_softmax_tile(const float* mpart, float* alpha_s, short* p_lds,
                             int slab, int wid, int col, int kgrp,
-                            const float (&sv)[4], float (&m_regs)[4],
-                            float (&l_regs)[4]) {
-  float m_tile[4];
+                            const float (&sv)[NREG], float (&m_regs)[NREG],
+                            float (&l_regs)[NREG]) {
+  float m_tile[NREG];
 #pragma unroll
-  for (int reg = 0; reg < 4; ++reg) {
+  for (int reg = 0; reg < NREG; ++reg) {
     const int row = kgrp * 4 + reg;
     float m = mpart[row];
 #pragma unroll
@@ -324,7 +350,7 @@ DEVINL bool pd_softmax_tile(const float* mpart, float* alpha_s, short* p_lds,
   // are skipped; P is bounded by e^THR (l/OT accumulate in fp32).
   bool grow = false;
 #pragma unroll
-  for (int reg = 0; reg < 4; ++reg) grow |= m_tile[reg] > m_regs[reg] + 8.0f;
+  for (int reg = 0; reg < NREG; ++reg) grow |= m_tile[reg] > m_regs[reg] + 8.0f;
 #ifdef LLMQ_DEFER_ON
   const bool rescale = __any(grow);
 #else
@@ -335,7 +361,7 @@ DEVINL bool pd_softmax_tile(const float* mpart, float* alpha_s, short* p_lds,
   const bool rescale = true; (void)grow;
 #endif
 #pragma unroll
-  for (int reg = 0; reg < 4; ++reg) {
+  for (int reg = 0; reg < NREG; ++reg) {
     const int row = kgrp * 4 + reg;
     const float m_new = rescale ? fmaxf(m_regs[reg], m_tile[reg]) : m_regs[reg];
     const float alpha = (rescale && m_new > -1e30f)
@@ -396,21 +422,21 @@ DEVINL void pd_pv_tile(const short* img, const short* p_lds,
 // Epilogue after the per-slab l partials are visible in l_part: sum l, then
 // either (gridDim.z > 1) write this z-block's UNNORMALISED fp32 partial rows
 // and their (m, l) stats to scratch, or normalise and store bf16 to out.
-template <int D, int SLABS, int DT>
+// OT column `col` is tile row col, i.e. q-head g = pd_row_head(col): both
+// paths index out / scratch by g (the merge kernel reads scratch rows by g).
+template <int D, int SLABS, int DT, int NREG>
 DEVINL void pd_store(__hip_bfloat16* out, float* scratch, const float* l_part,
-                     const f32x4_t (&ot)[DT], const float (&m_regs)[4], int b,
+                     const f32x4_t (&ot)[DT], const float (&m_regs)[NREG], int b,
                      int kh, int G, int num_kv_heads, long out_stride, int wid,
                      int col, int kgrp) {
   constexpr int D4 = DT * 16;  // dim slab per wave
   const int nsplit = gridDim.z;
-  float l_tot = l_part[col];
-#pragma unroll
-  for (int w = 1; w < SLABS; ++w) l_tot += l_part[w * 16 + col];
+  const int g = pd_row_head(col);
   if (nsplit > 1) {
     float* slot = scratch +
         ((((long)b * num_kv_heads + kh) * nsplit + blockIdx.z) * G) * (D + 2);
-    if (col < G) {
-      float* row = slot + (long)col * (D + 2);
+    if (g < G) {
+      float* row = slot + (long)g * (D + 2);
 #pragma unroll
       for (int dt = 0; dt < DT; ++dt) {
         const int dim0 = wid * D4 + dt * 16 + kgrp * 4;
@@ -418,14 +444,15 @@ DEVINL void pd_store(__hip_bfloat16* out, float* scratch, const float* l_part,
         for (int reg = 0; reg < 4; ++reg) row[dim0 + reg] = ot[dt][reg];
       }
     }
-    // Row stats: wave-0 lanes with col==0 cover rows r = kgrp*4+reg
-    // (m_regs is identical across waves after the shared-max combine).
+    // Row stats: wave-0 lanes with col==0 cover rows r = kgrp*4+reg, which
+    // hold heads reg*4+kgrp (wave 0 always runs the shared-max combine).
     if (wid == 0 && col == 0) {
 #pragma unroll
-      for (int reg = 0; reg < 4; ++reg) {
+      for (int reg = 0; reg < NREG; ++reg) {
         const int r = kgrp * 4 + reg;
-        if (r < G) {
-          float* row = slot + (long)r * (D + 2);
+        const int gr = reg * 4 + kgrp;
+        if (gr < G) {
+          float* row = slot + (long)gr * (D + 2);
           row[D] = m_regs[reg];
           float lt = l_part[r];
           for (int w = 1; w < SLABS; ++w) lt += l_part[w * 16 + r];
@@ -435,9 +462,12 @@ DEVINL void pd_store(__hip_bfloat16* out, float* scratch, const float* l_part,
     }
     return;
   }
-  const float inv = (l_tot > 0.f) ? 1.0f / l_tot : 0.f;
-  if (col < G) {
-    __hip_bfloat16* op = out + (long)b * out_stride + (long)(kh * G + col) * D;
+  if (g < G) {
+    float l_tot = l_part[col];
+#pragma unroll
+    for (int w = 1; w < SLABS; ++w) l_tot += l_part[w * 16 + col];
+    const float inv = (l_tot > 0.f) ? 1.0f / l_tot : 0.f;
+    __hip_bfloat16* op = out + (long)b * out_stride + (long)(kh * G + g) * D;
 #pragma unroll
     for (int dt = 0; dt < DT; ++dt) {
       const int dim0 = wid * D4 + dt * 16 + kgrp * 4;
@@ -455,7 +485,9 @@ DEVINL void pd_store(__hip_bfloat16* out, float* scratch, const float* l_part,
 // slice of the context and writes UNNORMALISED fp32 partials
 // (acc[G][D], m, l) to scratch[B][KVH][NSPLIT][G][D+2]; the
 // decode_splitkv_merge_kernel combines them. NSPLIT==1 writes out directly.
-template <int HEAD_DIM, int NW, typename TC = __hip_bfloat16>
+// NREG = softmax registers that hold q-heads (ceil(G/4) rounded to 1/2/4;
+// the launcher picks it from G).
+template <int HEAD_DIM, int NW, int NREG, typename TC = __hip_bfloat16>
 __global__ __launch_bounds__(NW * WAVE) void paged_decode_mfma_kernel(
     __hip_bfloat16* __restrict__ out,      // [B, H, D]
     const __hip_bfloat16* __restrict__ q,  // [B, H, D]
@@ -511,8 +543,9 @@ __global__ __launch_bounds__(NW * WAVE) void paged_decode_mfma_kernel(
   pd_load_qfrag<D, false>(qfrag, q, b, kh, G, q_stride, col, kgrp);
 
   // softmax state: every wave redundantly tracks rows r = kgrp*4 + reg
-  float m_regs[4] = {-1e30f, -1e30f, -1e30f, -1e30f};
-  float l_regs[4] = {0.f, 0.f, 0.f, 0.f};
+  float m_regs[NREG], l_regs[NREG];
+#pragma unroll
+  for (int reg = 0; reg < NREG; ++reg) { m_regs[reg] = -1e30f; l_regs[reg] = 0.f; }
   f32x4_t ot[DT];
 #pragma unroll
   for (int dt = 0; dt < DT; ++dt) ot[dt] = {0.f, 0.f, 0.f, 0.f};
@@ -521,6 +554,11 @@ __global__ __launch_bounds__(NW * WAVE) void paged_decode_mfma_kernel(
   pd_chunk_range<PD_KT>(L, window, start, range_lo, range_hi);
   constexpr int CPK = D / 8;    // 16B chunks per key row
   constexpr int NCK = PD_KT * CPK;
+  // block_size is 16 or 32 (launcher precondition): shift and mask, not
+  // a runtime divide, on every staged granule
+  const int bs_shift = 31 - __builtin_clz(block_size);
+  const int bs_mask = block_size - 1;
+  pd_init_pad_rows<NREG, PD_KT, NT>(p_lds, alpha_lds, tid);
   __syncthreads();  // bt_lds ready
 
   for (int base = range_lo; base < range_hi; base += PD_KT) {
@@ -531,10 +569,10 @@ __global__ __launch_bounds__(NW * WAVE) void paged_decode_mfma_kernel(
       const int dst = key * D + swz(key, d8);
       const int gkey = base + key;
       if (gkey < L) {
-        const int bidx = gkey / block_size;
+        const int bidx = gkey >> bs_shift;
         const long blk = (bidx < PD_MAX_BT) ? bt_lds[bidx] : bt_glob[bidx];
         const long rowoff =
-            ((blk * num_kv_heads + kh) * block_size + gkey % block_size) * D + d8;
+            ((blk * num_kv_heads + kh) * block_size + (gkey & bs_mask)) * D + d8;
         *reinterpret_cast<bf16x8_t*>(&kv_lds[dst]) = kv8_to_bf16(k_cache + rowoff);
       } else {
         *reinterpret_cast<bf16x8_t*>(&kv_lds[dst]) = bf16x8_t{0, 0, 0, 0, 0, 0, 0, 0};
@@ -555,11 +593,12 @@ __global__ __launch_bounds__(NW * WAVE) void paged_decode_mfma_kernel(
       }
     }
     // scale, softcap, bounds mask; rows r = kgrp*4 + reg
-    float sv[4], mx[4];
-    pd_scale_mask_rowmax(s, base + wid * 16 + col, L, start, scale, softcap, sv, mx);
+    float sv[NREG], mx[NREG];
+    pd_scale_mask_rowmax<NREG>(s, base + wid * 16 + col, L, start, scale, softcap,
+                               sv, mx);
     if (col == 0) {
 #pragma unroll
-      for (int reg = 0; reg < 4; ++reg) mpart_lds[wid][kgrp * 4 + reg] = mx[reg];
+      for (int reg = 0; reg < NREG; ++reg) mpart_lds[wid][kgrp * 4 + reg] = mx[reg];
     }
     __syncthreads();  // mparts ready; every wave is past its K reads
 
@@ -578,10 +617,10 @@ __global__ __launch_bounds__(NW * WAVE) void paged_decode_mfma_kernel(
                       (key & 3) * 16 + col0;
       const int gkey = base + key;
       if (gkey < L) {
-        const int bidx = gkey / block_size;
+        const int bidx = gkey >> bs_shift;
         const long blk = (bidx < PD_MAX_BT) ? bt_lds[bidx] : bt_glob[bidx];
         const long rowoff =
-            ((blk * num_kv_heads + kh) * block_size + gkey % block_size) * D + d8;
+            ((blk * num_kv_heads + kh) * block_size + (gkey & bs_mask)) * D + d8;
         *reinterpret_cast<bf16x8_t*>(&kv_lds[dst]) = kv8_to_bf16(v_cache + rowoff);
       } else {
         *reinterpret_cast<bf16x8_t*>(&kv_lds[dst]) = bf16x8_t{0, 0, 0, 0, 0, 0, 0, 0};
@@ -589,11 +628,11 @@ __global__ __launch_bounds__(NW * WAVE) void paged_decode_mfma_kernel(
     }
 
     // ---- combine maxes (identical on every wave), build P, update l
-    // Same arithmetic as pd_softmax_tile<NW, PD_KT> with slab == wid, kept
-    // as one fused loop: with NW max partials per row, the helper's
+    // Same arithmetic as pd_softmax_tile<NW, PD_KT, NREG> with slab == wid,
+    // kept as one fused loop: with NW max partials per row, the helper's
     // combine-all-rows-first order costs this kernel 14 VGPRs at D=256.
 #pragma unroll
-    for (int reg = 0; reg < 4; ++reg) {
+    for (int reg = 0; reg < NREG; ++reg) {
       const int row = kgrp * 4 + reg;
       float m_tile = mpart_lds[0][row];
 #pragma unroll
@@ -621,11 +660,11 @@ __global__ __launch_bounds__(NW * WAVE) void paged_decode_mfma_kernel(
   // ---- merge per-wave l, then store (normalised out, or raw partials)
   if (col == 0) {
 #pragma unroll
-    for (int reg = 0; reg < 4; ++reg) l_lds[wid][kgrp * 4 + reg] = l_regs[reg];
+    for (int reg = 0; reg < NREG; ++reg) l_lds[wid][kgrp * 4 + reg] = l_regs[reg];
   }
   __syncthreads();
-  pd_store<D, NW, DT>(out, scratch, &l_lds[0][0], ot, m_regs, b, kh, G,
-                      num_kv_heads, out_stride, wid, col, kgrp);
+  pd_store<D, NW, DT, NREG>(out, scratch, &l_lds[0][0], ot, m_regs, b, kh, G,
+                            num_kv_heads, out_stride, wid, col, kgrp);
 }
 
 // -------------------------------------------- pipelined MFMA paged decode --
@@ -658,7 +697,7 @@ __global__ __launch_bounds__(NW * WAVE) void paged_decode_mfma_kernel(
 // occupancy below that (the r1 lesson: this kernel is governed by
 // waves/SIMD, every latency trick that cost occupancy lost). The 128-key
 // chunk is 1 workgroup/CU by LDS (2 waves/SIMD) — let it use 196.
-template <int HEAD_DIM, int NW, int PD_KT>
+template <int HEAD_DIM, int NW, int PD_KT, int NREG>
 __global__ __launch_bounds__(NW * WAVE, (PD_KT <= 64 ? 4 : 2)) void paged_decode_pipe_kernel(
     __hip_bfloat16* __restrict__ out,      // [B, H, D]
     const __hip_bfloat16* __restrict__ q,  // [B, H, D]
@@ -672,7 +711,7 @@ __global__ __launch_bounds__(NW * WAVE, (PD_KT <= 64 ? 4 : 2)) void paged_decode
   constexpr int D = HEAD_DIM;
   constexpr int KS = D / 32;        // MFMA K-steps over the head dim
   constexpr int NT = NW * WAVE;     // threads per workgroup
-  constexpr int SLABS = PD_KT / 16; // 16-key S slabs (<= NW; waves duplicate)
+  constexpr int SLABS = PD_KT / 16; // 16-key S slabs (<= NW; extra waves skip S)
   constexpr int D4 = D / NW;        // dim slab per wave (PV)
   constexpr int DT = D4 / 16;       // 16-dim MFMA tiles per wave
   constexpr int CPK = D / 8;        // 16B granules per key row
@@ -695,6 +734,25 @@ __global__ __launch_bounds__(NW * WAVE, (PD_KT <= 64 ? 4 : 2)) void paged_decode
   const int col = lane & 15;
   const int kgrp = lane >> 4;
   const int slab = wid % SLABS;
+  // Waves beyond the S slabs (64-key chunks: waves 4..7 of 8) have no slab
+  // of their own: their S, softcap, row max and softmax would repeat a
+  // lower wave's, on the same SIMD, and nothing reads the copy. They skip
+  // that work (wave-uniform branches, no barrier inside) and still reach
+  // every barrier, issue their share of the DMA and run PV. The defer-max
+  // build keeps the copies: its ballot needs m_regs current on every wave.
+#ifdef LLMQ_DEFER_ON
+  constexpr bool s_wave = true;
+#else
+  const bool s_wave =
+      SLABS == NW || __builtin_amdgcn_readfirstlane(wid) < SLABS;
+#endif
+  // block_size is 16 or 32 (launcher precondition): shift and mask, not a
+  // runtime divide, in every DMA source address; the kv-head base and the
+  // per-block stride are chunk-invariant scalars
+  const int bs_shift = 31 - __builtin_clz(block_size);
+  const int bs_mask = block_size - 1;
+  const long blk_stride = (long)num_kv_heads * block_size * D;
+  const long head_off = (long)kh * block_size * D;
 
   // ONE shared array (guide §5 trap 4a: a second __shared__ object makes
   // hipcc drain vmcnt(0) before every ds_read while a glds is in flight).
@@ -727,8 +785,10 @@ __global__ __launch_bounds__(NW * WAVE, (PD_KT <= 64 ? 4 : 2)) void paged_decode
   bf16x8_t qfrag[KS];
   pd_load_qfrag<D, true>(qfrag, q, b, kh, G, q_stride, col, kgrp);
 
-  float m_regs[4] = {-1e30f, -1e30f, -1e30f, -1e30f};
-  float l_regs[4] = {0.f, 0.f, 0.f, 0.f};
+  float m_regs[NREG], l_regs[NREG];
+#pragma unroll
+  for (int reg = 0; reg < NREG; ++reg) { m_regs[reg] = -1e30f; l_regs[reg] = 0.f; }
+  pd_init_pad_rows<NREG, PD_KT, NT>(p_lds2, alpha_s, tid);
   f32x4_t ot[DT];
 #pragma unroll
   for (int dt = 0; dt < DT; ++dt) ot[dt] = {0.f, 0.f, 0.f, 0.f};
@@ -748,9 +808,8 @@ __global__ __launch_bounds__(NW * WAVE, (PD_KT <= 64 ? 4 : 2)) void paged_decode
     const int r8 = (g % CPK) * 8;
     const int d = r8 ^ ((key & 7) << 3);
     const int gkey = min(base + key, L - 1);
-    const long blk = bt_l[gkey / block_size];
-    return k_cache + (blk * num_kv_heads + kh) * ((long)block_size * D) +
-           (long)(gkey % block_size) * D + d;
+    const long blk = bt_l[gkey >> bs_shift];
+    return k_cache + head_off + blk * blk_stride + ((gkey & bs_mask) * D + d);
   };
   // V: subtile st, in-subtile granule = lane (tr16 image inverse mapping).
   auto v_src = [&](int base, int st) -> const __hip_bfloat16* {
@@ -761,25 +820,33 @@ __global__ __launch_bounds__(NW * WAVE, (PD_KT <= 64 ? 4 : 2)) void paged_decode
     const int key = ks * 32 + qq * 4 + rem / 16;
     const int dim = dtile * 16 + (rem & 15);
     const int gkey = min(base + key, L - 1);
-    const long blk = bt_l[gkey / block_size];
-    return v_cache + (blk * num_kv_heads + kh) * ((long)block_size * D) +
-           (long)(gkey % block_size) * D + dim;
+    const long blk = bt_l[gkey >> bs_shift];
+    return v_cache + head_off + blk * blk_stride + ((gkey & bs_mask) * D + dim);
   };
 
+  // All source addresses first, then the DMAs back to back: glds16 is an
+  // asm with a memory clobber, so a block-table read placed between two of
+  // them cannot be batched or shared with its neighbours by the compiler.
   auto issue_k = [&](int base, short* dst) {
+    const __hip_bfloat16* src[NI_K];
+#pragma unroll
+    for (int j = 0; j < NI_K; ++j) src[j] = k_src(base, (wid * NI_K + j) * 64 + lane);
 #pragma unroll
     for (int j = 0; j < NI_K; ++j) {
-      const int inst = wid * NI_K + j;
-      const int off = __builtin_amdgcn_readfirstlane(inst * 512);
-      glds16(k_src(base, inst * 64 + lane), dst + off);
+      const int off = __builtin_amdgcn_readfirstlane((wid * NI_K + j) * 512);
+      glds16(src[j], dst + off);
     }
   };
+  // A wave's NI_V subtiles are consecutive 16-dim tiles of ONE 32-key group,
+  // so its lanes read the same cache row for all of them: one row address
+  // per chunk, then a 16-element step per subtile.
+  static_assert((D / 16) % NI_V == 0, "a wave's V subtiles share their keys");
   auto issue_v = [&](int base, short* dst) {
+    const __hip_bfloat16* const row = v_src(base, wid * NI_V);
 #pragma unroll
     for (int j = 0; j < NI_V; ++j) {
-      const int st = wid * NI_V + j;
-      const int off = __builtin_amdgcn_readfirstlane(st * 528);
-      glds16(v_src(base, st), dst + off);
+      const int off = __builtin_amdgcn_readfirstlane((wid * NI_V + j) * 528);
+      glds16(row + j * 16, dst + off);
     }
   };
   // ---- prologue: block table visible, then K(first) in flight
@@ -792,9 +859,10 @@ __global__ __launch_bounds__(NW * WAVE, (PD_KT <= 64 ? 4 : 2)) void paged_decode
     short* const Y = cur ? kv0 : kv1;
     pipe_barrier_vm<0>();  // K(base) landed (all waves)
 
-    // ---- S[16,16] for this wave's slab (waves wid>=SLABS duplicate)
-    f32x4_t s = {0.f, 0.f, 0.f, 0.f};
-    {
+    // ---- S[16,16] for this wave's slab
+    float sv[NREG];
+    if (s_wave) {
+      f32x4_t s = {0.f, 0.f, 0.f, 0.f};
       const int key = slab * 16 + col;
 #pragma unroll
       for (int ks = 0; ks < KS; ++ks) {
@@ -803,12 +871,12 @@ __global__ __launch_bounds__(NW * WAVE, (PD_KT <= 64 ? 4 : 2)) void paged_decode
             *reinterpret_cast<const bf16x8_t*>(&X[key * D + swz(key, d8)]);
         s = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qfrag[ks], bfrag, s, 0, 0, 0);
       }
-    }
-    float sv[4], mx[4];
-    pd_scale_mask_rowmax(s, base + slab * 16 + col, L, start, scale, softcap, sv, mx);
-    if (col == 0 && wid < SLABS) {
+      float mx[NREG];
+      pd_scale_mask_rowmax<NREG>(s, base + key, L, start, scale, softcap, sv, mx);
+      if (col == 0 && wid < SLABS) {
 #pragma unroll
-      for (int reg = 0; reg < 4; ++reg) mpart[slab * 16 + kgrp * 4 + reg] = mx[reg];
+        for (int reg = 0; reg < NREG; ++reg) mpart[slab * 16 + kgrp * 4 + reg] = mx[reg];
+      }
     }
     pipe_barrier();  // S reads of X done everywhere; mpart visible
 
@@ -818,9 +886,11 @@ __global__ __launch_bounds__(NW * WAVE, (PD_KT <= 64 ? 4 : 2)) void paged_decode
     issue_v(base, X);
     if (prefetch) issue_k(next, Y);
 
-    // ---- combine maxes, build P, update l (redundant on every wave)
-    const bool rescale = pd_softmax_tile<SLABS, PD_KT>(
-        mpart, alpha_s, p_lds2, slab, wid, col, kgrp, sv, m_regs, l_regs);
+    // ---- combine maxes, build P, update l (one wave per slab)
+    bool rescale = true;
+    if (s_wave)
+      rescale = pd_softmax_tile<SLABS, PD_KT, NREG>(
+          mpart, alpha_s, p_lds2, slab, wid, col, kgrp, sv, m_regs, l_regs);
     if (prefetch) {
       pipe_barrier_vm<NI_K>();  // V landed; K(next) stays in flight
     } else {
@@ -837,11 +907,11 @@ __global__ __launch_bounds__(NW * WAVE, (PD_KT <= 64 ? 4 : 2)) void paged_decode
   // ---- merge per-slab l, then store (normalised out, or raw partials)
   if (col == 0 && wid < SLABS) {
 #pragma unroll
-    for (int reg = 0; reg < 4; ++reg) l_part[slab * 16 + kgrp * 4 + reg] = l_regs[reg];
+    for (int reg = 0; reg < NREG; ++reg) l_part[slab * 16 + kgrp * 4 + reg] = l_regs[reg];
   }
   pipe_barrier();
-  pd_store<D, SLABS, DT>(out, scratch, l_part, ot, m_regs, b, kh, G,
-                         num_kv_heads, out_stride, wid, col, kgrp);
+  pd_store<D, SLABS, DT, NREG>(out, scratch, l_part, ot, m_regs, b, kh, G,
+                               num_kv_heads, out_stride, wid, col, kgrp);
 }
 
 // --------------------------------------- fp8-KV pipelined MFMA decode --
@@ -863,7 +933,7 @@ __global__ __launch_bounds__(NW * WAVE, (PD_KT <= 64 ? 4 : 2)) void paged_decode
 // Y-front K(i+1) and Y-back V(i)raw are disjoint ranges. LDS stays at
 // 2 × image + p + bt ≈ 74 KB -> 2 workgroups/CU, same as the bf16 pipe.
 
-template <int HEAD_DIM, int NW>
+template <int HEAD_DIM, int NW, int NREG>
 __global__ __launch_bounds__(NW * WAVE, 4) void paged_decode_pipe_fp8_kernel(
     __hip_bfloat16* __restrict__ out,      // [B, H, D]
     const __hip_bfloat16* __restrict__ q,  // [B, H, D]
@@ -878,7 +948,7 @@ __global__ __launch_bounds__(NW * WAVE, 4) void paged_decode_pipe_fp8_kernel(
   constexpr int KS = D / 32;
   constexpr int PD_KT = 64;
   constexpr int NT = NW * WAVE;
-  constexpr int SLABS = PD_KT / 16;     // 4 (waves duplicate when NW=8)
+  constexpr int SLABS = PD_KT / 16;     // 4 (waves 4..7 skip S when NW=8)
   constexpr int D4 = D / NW;
   constexpr int DT = D4 / 16;
   constexpr int G16B = D / 16;          // 16B granules per fp8 key row
@@ -903,6 +973,25 @@ __global__ __launch_bounds__(NW * WAVE, 4) void paged_decode_pipe_fp8_kernel(
   const int col = lane & 15;
   const int kgrp = lane >> 4;
   const int slab = wid % SLABS;
+  // Waves beyond the S slabs (64-key chunks: waves 4..7 of 8) have no slab
+  // of their own: their S, softcap, row max and softmax would repeat a
+  // lower wave's, on the same SIMD, and nothing reads the copy. They skip
+  // that work (wave-uniform branches, no barrier inside) and still reach
+  // every barrier, issue their share of the DMA and run PV. The defer-max
+  // build keeps the copies: its ballot needs m_regs current on every wave.
+#ifdef LLMQ_DEFER_ON
+  constexpr bool s_wave = true;
+#else
+  const bool s_wave =
+      SLABS == NW || __builtin_amdgcn_readfirstlane(wid) < SLABS;
+#endif
+  // block_size is 16 or 32 (launcher precondition): shift and mask, not a
+  // runtime divide, in every DMA source address; the kv-head base and the
+  // per-block stride are chunk-invariant scalars
+  const int bs_shift = 31 - __builtin_clz(block_size);
+  const int bs_mask = block_size - 1;
+  const long blk_stride = (long)num_kv_heads * block_size * D;
+  const long head_off = (long)kh * block_size * D;
 
   constexpr int P_OFF = 2 * IMG_ELEMS;                   // shorts
   constexpr int F_BASE = (P_OFF + 16 * PD_KT + 7) / 8 * 4;
@@ -929,8 +1018,10 @@ __global__ __launch_bounds__(NW * WAVE, 4) void paged_decode_pipe_fp8_kernel(
   bf16x8_t qfrag[KS];
   pd_load_qfrag<D, true>(qfrag, q, b, kh, G, q_stride, col, kgrp);
 
-  float m_regs[4] = {-1e30f, -1e30f, -1e30f, -1e30f};
-  float l_regs[4] = {0.f, 0.f, 0.f, 0.f};
+  float m_regs[NREG], l_regs[NREG];
+#pragma unroll
+  for (int reg = 0; reg < NREG; ++reg) { m_regs[reg] = -1e30f; l_regs[reg] = 0.f; }
+  pd_init_pad_rows<NREG, PD_KT, NT>(p_lds2, alpha_s, tid);
   f32x4_t ot[DT];
 #pragma unroll
   for (int dt = 0; dt < DT; ++dt) ot[dt] = {0.f, 0.f, 0.f, 0.f};
@@ -940,33 +1031,43 @@ __global__ __launch_bounds__(NW * WAVE, 4) void paged_decode_pipe_fp8_kernel(
 
   auto kv_row = [&](int gkey, const __hip_fp8_e4m3* cache) -> const __hip_fp8_e4m3* {
     const int ck = min(gkey, L - 1);  // clamp: finite real data (masked)
-    const long blk = bt_l[ck / block_size];
-    return cache + (blk * num_kv_heads + kh) * ((long)block_size * D) +
-           (long)(ck % block_size) * D;
+    const long blk = bt_l[ck >> bs_shift];
+    return cache + head_off + blk * blk_stride + (ck & bs_mask) * D;
   };
   // K fp8 image: [PD_KT][D] bytes, 16B-granule XOR swizzle (col16 ^ key&7)
+  // (both issue all source addresses first, then the DMAs back to back:
+  // see the bf16 pipe kernel)
   auto issue_k = [&](int base, short* dst) {
+    const __hip_fp8_e4m3* src[NI_K];
 #pragma unroll
     for (int j = 0; j < NI_K; ++j) {
       const int g = (wid * NI_K + j) * 64 + lane;  // 16B granule
       const int key = g / G16B;
       const int c16 = g % G16B;
       const int src_col = ((c16 ^ (key & 7)) & (G16B - 1)) << 4;
+      src[j] = kv_row(base + key, k_cache) + src_col;
+    }
+#pragma unroll
+    for (int j = 0; j < NI_K; ++j) {
       const int off = __builtin_amdgcn_readfirstlane((wid * NI_K + j) * 512);
-      glds16(kv_row(base + key, k_cache) + src_col,
-             reinterpret_cast<char*>(dst) + off * 2);
+      glds16(src[j], reinterpret_cast<char*>(dst) + off * 2);
     }
   };
   // V raw fp8, linear [PD_KT][D] bytes into the back half of `dst`
   auto issue_v_raw = [&](int base, short* dst) {
     char* const back = reinterpret_cast<char*>(dst) + RAW_BYTES;
+    const __hip_fp8_e4m3* src[NI_VR];
 #pragma unroll
     for (int j = 0; j < NI_VR; ++j) {
       const int g = (wid * NI_VR + j) * 64 + lane;
       const int key = g / G16B;
       const int colb = (g % G16B) * 16;
+      src[j] = kv_row(base + key, v_cache) + colb;
+    }
+#pragma unroll
+    for (int j = 0; j < NI_VR; ++j) {
       const int off = __builtin_amdgcn_readfirstlane((wid * NI_VR + j) * 1024);
-      glds16(kv_row(base + key, v_cache) + colb, back + off);
+      glds16(src[j], back + off);
     }
   };
 
@@ -980,8 +1081,9 @@ __global__ __launch_bounds__(NW * WAVE, 4) void paged_decode_pipe_fp8_kernel(
     pipe_barrier_vm<0>();  // K(base) landed in X front
 
     // ---- S from fp8 K (convert per fragment with packed cvt VOPs)
-    f32x4_t s = {0.f, 0.f, 0.f, 0.f};
-    {
+    float sv[NREG];
+    if (s_wave) {
+      f32x4_t s = {0.f, 0.f, 0.f, 0.f};
       const int key = slab * 16 + col;
       const char* krow = reinterpret_cast<const char*>(X) + key * D;
 #pragma unroll
@@ -993,12 +1095,12 @@ __global__ __launch_bounds__(NW * WAVE, 4) void paged_decode_pipe_fp8_kernel(
         const bf16x8_t bfrag = fp8x8_to_bf16(raw.x, raw.y);
         s = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qfrag[ks], bfrag, s, 0, 0, 0);
       }
-    }
-    float sv[4], mx[4];
-    pd_scale_mask_rowmax(s, base + slab * 16 + col, L, start, scale, softcap, sv, mx);
-    if (col == 0 && wid < SLABS) {
+      float mx[NREG];
+      pd_scale_mask_rowmax<NREG>(s, base + key, L, start, scale, softcap, sv, mx);
+      if (col == 0 && wid < SLABS) {
 #pragma unroll
-      for (int reg = 0; reg < 4; ++reg) mpart[slab * 16 + kgrp * 4 + reg] = mx[reg];
+        for (int reg = 0; reg < NREG; ++reg) mpart[slab * 16 + kgrp * 4 + reg] = mx[reg];
+      }
     }
     pipe_barrier();  // S reads of X-front done; mparts visible
 
@@ -1010,9 +1112,11 @@ __global__ __launch_bounds__(NW * WAVE, 4) void paged_decode_pipe_fp8_kernel(
     issue_v_raw(base, Y);
     if (prefetch) issue_k(next, Y);
 
-    // ---- softmax combine + P
-    const bool rescale = pd_softmax_tile<SLABS, PD_KT>(
-        mpart, alpha_s, p_lds2, slab, wid, col, kgrp, sv, m_regs, l_regs);
+    // ---- softmax combine + P (one wave per slab)
+    bool rescale = true;
+    if (s_wave)
+      rescale = pd_softmax_tile<SLABS, PD_KT, NREG>(
+          mpart, alpha_s, p_lds2, slab, wid, col, kgrp, sv, m_regs, l_regs);
     if (prefetch) {
       pipe_barrier_vm<NI_K>();  // V raw landed; K(next) stays in flight
     } else {
@@ -1048,11 +1152,11 @@ __global__ __launch_bounds__(NW * WAVE, 4) void paged_decode_pipe_fp8_kernel(
   // ---- merge per-slab l, then store (normalised out, or raw partials)
   if (col == 0 && wid < SLABS) {
 #pragma unroll
-    for (int reg = 0; reg < 4; ++reg) l_part[slab * 16 + kgrp * 4 + reg] = l_regs[reg];
+    for (int reg = 0; reg < NREG; ++reg) l_part[slab * 16 + kgrp * 4 + reg] = l_regs[reg];
   }
   pipe_barrier();
-  pd_store<D, SLABS, DT>(out, scratch, l_part, ot, m_regs, b, kh, G,
-                         num_kv_heads, out_stride, wid, col, kgrp);
+  pd_store<D, SLABS, DT, NREG>(out, scratch, l_part, ot, m_regs, b, kh, G,
+                               num_kv_heads, out_stride, wid, col, kgrp);
 }
 
 // Combine split-KV partials: out[b, kh*G+g] = Σ_s w_s·acc_s / Σ_s w_s·l_s,
