@@ -11,6 +11,7 @@ one replay + one sampler call regardless of model depth.
 from __future__ import annotations
 
 import logging
+import os
 import time
 from typing import Dict, List, Optional, Tuple
 
@@ -64,6 +65,13 @@ class ModelRunner:
         # decode path, "prefill" for the prefill segment of an OVERLAPPED
         # split mixed step — two concurrent streams must not share them).
         self._sample_bufs: Dict[str, Dict[str, torch.Tensor]] = {}
+        # GPU logit tail: the sampler kernels read the lm_head GEMM's output
+        # in the model dtype and apply the final soft-cap in registers, so no
+        # fp32 [B, vocab] matrix is ever materialised. LLMQ_FUSED_LOGIT_TAIL=0
+        # keeps the eager tail (compute_logits: widen, / cap, tanh, * cap)
+        # for comparison; both sample identical tokens.
+        self.fused_logit_tail = device.type == "cuda" and os.environ.get(
+            "LLMQ_FUSED_LOGIT_TAIL", "1") not in ("0", "false", "")
         if self.use_graphs:
             self._alloc_static_buffers()
 
@@ -210,9 +218,9 @@ class ModelRunner:
         if not rel_last:
             return torch.empty(0, dtype=torch.long, device=dev)
         last_hidden = hidden[torch.tensor(rel_last, dtype=torch.long, device=dev)]
-        logits = self.model.compute_logits(last_hidden)
+        logits, cap = self._logits_for_sampling(last_hidden)
         sample_seqs = [s for s, (st, e) in zip(seqs, chunks) if e == s.num_tokens]
-        return self._sample(logits, sample_seqs, buf_name)
+        return self._sample(logits, sample_seqs, buf_name, softcap=cap)
 
     # -- mixed (decode rows + ride-along prefill rows, eager) ------------
 
@@ -263,11 +271,11 @@ class ModelRunner:
         hidden = self.model.forward(input_ids, positions, self.kv_cache, meta)
         last_idx = list(range(nd)) + [nd + r for r in rel_last]
         last_hidden = hidden[torch.tensor(last_idx, dtype=torch.long, device=dev)]
-        logits = self.model.compute_logits(last_hidden)
+        logits, cap = self._logits_for_sampling(last_hidden)
         sample_seqs = list(dseqs) + [
             s for s, (st, e) in zip(pseqs, chunks) if e == s.num_tokens
         ]
-        return self._sample(logits, sample_seqs)
+        return self._sample(logits, sample_seqs, softcap=cap)
 
     # -- decode ----------------------------------------------------------
 
@@ -300,8 +308,8 @@ class ModelRunner:
         input_ids = torch.tensor(ids, dtype=torch.long, device=dev)
         positions = torch.tensor(pos, dtype=torch.long, device=dev)
         hidden = self.model.forward(input_ids, positions, self.kv_cache, meta)
-        logits = self.model.compute_logits(hidden)
-        return self._sample(logits, seqs)
+        logits, cap = self._logits_for_sampling(hidden)
+        return self._sample(logits, seqs, softcap=cap)
 
     def _decode_with_graph(
         self, seqs: List[Sequence], bucket: int, ids, pos, slots, ctx
@@ -345,8 +353,8 @@ class ModelRunner:
             self.h_block_tables[:bucket, :max_w], non_blocking=True
         )
         self._graphs[bucket].replay()
-        logits = self.model.compute_logits(self.out_hidden[:B])
-        return self._sample(logits, seqs)
+        logits, cap = self._logits_for_sampling(self.out_hidden[:B])
+        return self._sample(logits, seqs, softcap=cap)
 
     # -- sampling --------------------------------------------------------
 
@@ -367,8 +375,17 @@ class ModelRunner:
             self._sample_bufs[name] = buf
         return buf
 
+    def _logits_for_sampling(self, hidden: torch.Tensor) -> Tuple[torch.Tensor, float]:
+        """(logits, softcap) for _sample: the raw lm_head output plus the cap
+        the sampler kernels still have to apply, or fully formed fp32 logits
+        and 0 (CPU, LLMQ_FUSED_LOGIT_TAIL=0)."""
+        if self.fused_logit_tail:
+            cap = self.model.spec.final_softcap
+            return self.model.lm_head_logits(hidden), float(cap) if cap and cap > 0 else 0.0
+        return self.model.compute_logits(hidden), 0.0
+
     def _sample(self, logits: torch.Tensor, seqs: List[Sequence],
-                buf_name: str = "main") -> torch.Tensor:
+                buf_name: str = "main", softcap: float = 0.0) -> torch.Tensor:
         dev = logits.device
         self._sample_step += 1
         simple = all(
@@ -396,7 +413,8 @@ class ModelRunner:
             buf["temps"][:B].copy_(th[:B], non_blocking=True)
             buf["seeds"][:B].copy_(sh[:B], non_blocking=True)
             buf["pos"][:B].copy_(ph[:B], non_blocking=True)
-            logits_f = logits.float()
+            # fused tail: logits stay in the GEMM's dtype (no fp32 copy)
+            logits_f = logits if self.fused_logit_tail else logits.float()
             bounds = None
             if not simple:
                 tps = torch.tensor([s.params.top_p for s in seqs],
@@ -404,11 +422,12 @@ class ModelRunner:
                 tks = torch.tensor([s.params.top_k for s in seqs],
                                    dtype=torch.int64, device=dev)
                 bounds = ops.topk_topp_bound(
-                    logits_f, buf["temps"][:B], tps, tks)
+                    logits_f, buf["temps"][:B], tps, tks, softcap)
             ops.sample_gumbel_argmax(
                 buf["out"][:B], buf["keys"][:B], logits_f,
                 buf["temps"][:B], buf["seeds"][:B],
                 buf["pos"][:B], self.config.seed, self._sample_step, bounds,
+                softcap,
             )
             return buf["out"][:B]
         temps = torch.tensor([s.params.temperature for s in seqs], dtype=torch.float32, device=dev)

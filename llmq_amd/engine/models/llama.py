@@ -315,6 +315,13 @@ class CausalLM:
         return h
 
     @torch.no_grad()
+    def lm_head_logits(self, hidden: torch.Tensor) -> torch.Tensor:
+        """hidden [N, hidden] → the lm_head GEMM's output [N, vocab] in the
+        model dtype: not widened, final soft-cap NOT applied. For the fused
+        GPU sampler, which does both on the values it loads."""
+        return _proj(hidden, self.lm_head)
+
+    @torch.no_grad()
     def compute_logits(self, hidden: torch.Tensor) -> torch.Tensor:
         """hidden [N, hidden] → logits [N, vocab] (fp32)."""
         logits = _proj(hidden, self.lm_head).float()

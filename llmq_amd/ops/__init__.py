@@ -256,37 +256,43 @@ def skinny_gemm(
 def sample_gumbel_argmax(
     out: torch.Tensor,        # [B] int64
     keys: torch.Tensor,       # [B] int64 scratch (packed value|~index)
-    logits: torch.Tensor,     # [B, V] fp32
+    logits: torch.Tensor,     # [B, V] fp32, or bf16/fp16 as the GEMM wrote them
     temps: torch.Tensor,      # [B] fp32 (<= 0 → greedy row)
     req_seeds: torch.Tensor,  # [B] int32 (0 = unseeded)
     req_pos: torch.Tensor,    # [B] int32 output position (seeded rows)
     seed: int,
     step: int,
     bounds: Optional[torch.Tensor] = None,  # [B] fp32 top-k/p keep-bound
+    softcap: float = 0.0,     # > 0: sample from cap * tanh(logit / cap)
 ) -> None:
     """Fused one-pass sampler: per-row Gumbel-max (== softmax sampling) or
     argmax for greedy rows, optionally truncated to {logit >= bounds[b]}
     (top-k/top-p, from topk_topp_bound). Unseeded rows draw from the
     counter-based (engine seed, step, row) stream; rows with a request seed
     draw from (request_seed, output_position) — reproducible for a given
-    request regardless of batch placement."""
+    request regardless of batch placement. The kernel widens the logits and
+    applies the final soft-cap in registers: tokens equal those sampled from
+    `torch.tanh(logits.float() / softcap) * softcap`."""
     assert _use_hip(logits)
     keys.zero_()
     _EXT.sample_gumbel_argmax(out, keys, logits, temps, req_seeds, req_pos,
-                              seed, step, bounds)
+                              seed, step, bounds, softcap)
 
 
 def topk_topp_bound(
-    logits: torch.Tensor,   # [B, V] fp32
+    logits: torch.Tensor,   # [B, V] fp32, or bf16/fp16 as the GEMM wrote them
     temps: torch.Tensor,    # [B] fp32
     top_ps: torch.Tensor,   # [B] fp32
     top_ks: torch.Tensor,   # [B] int64 (0 = off)
+    softcap: float = 0.0,   # > 0: bound on cap * tanh(logit / cap)
 ) -> torch.Tensor:
     """Per-row logit-space keep-bound realising top-p ∧ top-k truncation
-    via histogram select (3 streaming passes; no full-vocab sort)."""
+    via histogram select (3 streaming passes; no full-vocab sort). With a
+    soft-cap the bound is in capped-logit space, the space the sampler
+    compares in when given the same `softcap`."""
     assert _use_hip(logits)
     out = torch.empty(logits.size(0), dtype=torch.float32, device=logits.device)
-    _EXT.topk_topp_bound(out, logits, temps, top_ps, top_ks)
+    _EXT.topk_topp_bound(out, logits, temps, top_ps, top_ks, softcap)
     return out
 
 

@@ -140,13 +140,31 @@ void norm_add_norm(at::Tensor x, at::Tensor residual, at::Tensor w_post,
   CHECK_LASTDIM(x);
   const int hidden = x.size(-1);
   const long rows = x.numel() / hidden;
+  // Rows of up to 8192 bf16/half values are held in registers (2 or 4
+  // 16-byte vectors per thread); anything else takes the three-trip kernel.
+  // LLMQ_NORM_SANDWICH_REGS=0 selects the three-trip kernel everywhere (A/B
+  // and the bitwise-equality test). Read per call, like LLMQ_DECODE_PIPE.
+  const char* re = getenv("LLMQ_NORM_SANDWICH_REGS");
+  const bool regs = (!re || atoi(re) != 0) && x.element_size() == 2 &&
+                    hidden % 8 == 0 && hidden <= 8192;
   dispatch_dtype(x, "norm_add_norm", [&]<typename T>() {
-    hipLaunchKernelGGL(norm_add_norm_kernel<T>, dim3(rows), dim3(256), 0,
-                       stream(), reinterpret_cast<T*>(x.data_ptr()),
-                       reinterpret_cast<T*>(residual.data_ptr()),
-                       reinterpret_cast<const T*>(w_post.data_ptr()),
-                       reinterpret_cast<const T*>(w_pre.data_ptr()), hidden,
-                       (float)eps, (float)offset);
+    auto launch = [&](void (*kernel)(T*, T*, const T*, const T*, int, float,
+                                     float)) {
+      hipLaunchKernelGGL(kernel, dim3(rows), dim3(256), 0, stream(),
+                         reinterpret_cast<T*>(x.data_ptr()),
+                         reinterpret_cast<T*>(residual.data_ptr()),
+                         reinterpret_cast<const T*>(w_post.data_ptr()),
+                         reinterpret_cast<const T*>(w_pre.data_ptr()), hidden,
+                         (float)eps, (float)offset);
+    };
+    if constexpr (sizeof(T) == 2) {
+      if (regs) {
+        launch(hidden <= 4096 ? norm_add_norm_regs_kernel<T, 2>
+                              : norm_add_norm_regs_kernel<T, 4>);
+        return;
+      }
+    }
+    launch(norm_add_norm_kernel<T>);
   });
 }
 
@@ -469,26 +487,42 @@ void skinny_gemm(at::Tensor out, at::Tensor x, at::Tensor w,
 
 // ------------------------------------------------------------- sampling --
 
+// Logits arrive as the lm_head GEMM stored them (bf16/half) or as fp32;
+// softcap > 0 applies cap * tanh(x / cap) in registers (logit_value), with
+// the reciprocal formed here in fp32 as torch forms it for `logits / cap`.
+float softcap_reciprocal(double softcap) {
+  return softcap > 0 ? 1.0f / (float)softcap : 0.0f;
+}
+
 void topk_topp_bound(at::Tensor out_bound, at::Tensor logits, at::Tensor temps,
-                     at::Tensor top_ps, at::Tensor top_ks) {
+                     at::Tensor top_ps, at::Tensor top_ks, double softcap) {
   CHECK_GPU(logits);
-  TORCH_CHECK(logits.scalar_type() == at::kFloat && logits.dim() == 2);
+  CHECK_LASTDIM(logits);
+  TORCH_CHECK(logits.dim() == 2);
   TORCH_CHECK(out_bound.scalar_type() == at::kFloat);
+  TORCH_CHECK(temps.scalar_type() == at::kFloat);
   TORCH_CHECK(top_ps.scalar_type() == at::kFloat);
   TORCH_CHECK(top_ks.scalar_type() == at::kLong);
   const int B = logits.size(0), V = logits.size(1);
-  hipLaunchKernelGGL(topk_topp_bound_kernel, dim3(B), dim3(256), 0, stream(),
-                     out_bound.data_ptr<float>(), logits.data_ptr<float>(),
-                     temps.data_ptr<float>(), top_ps.data_ptr<float>(),
-                     top_ks.data_ptr<long>(), V, logits.stride(0));
+  if (B == 0) return;
+  dispatch_dtype(logits, "topk_topp_bound", [&]<typename T>() {
+    hipLaunchKernelGGL(topk_topp_bound_kernel<T>, dim3(B), dim3(256), 0,
+                       stream(), out_bound.data_ptr<float>(),
+                       reinterpret_cast<const T*>(logits.data_ptr()),
+                       temps.data_ptr<float>(), top_ps.data_ptr<float>(),
+                       top_ks.data_ptr<long>(), V, logits.stride(0),
+                       (float)softcap, softcap_reciprocal(softcap));
+  });
 }
 
 void sample_gumbel_argmax(at::Tensor out, at::Tensor keys, at::Tensor logits,
                           at::Tensor temps, at::Tensor req_seeds,
                           at::Tensor req_pos, long seed, long step,
-                          c10::optional<at::Tensor> bounds) {
+                          c10::optional<at::Tensor> bounds, double softcap) {
   CHECK_GPU(logits);
-  TORCH_CHECK(logits.scalar_type() == at::kFloat && logits.dim() == 2);
+  CHECK_LASTDIM(logits);
+  TORCH_CHECK(logits.dim() == 2);
+  TORCH_CHECK(temps.scalar_type() == at::kFloat);
   TORCH_CHECK(out.scalar_type() == at::kLong);
   TORCH_CHECK(keys.scalar_type() == at::kLong && keys.numel() == logits.size(0));
   TORCH_CHECK(req_seeds.scalar_type() == at::kInt);
@@ -502,13 +536,19 @@ void sample_gumbel_argmax(at::Tensor out, at::Tensor keys, at::Tensor logits,
   // enough splits to fill the chip at small B
   int nsplit = 1;
   while (B * nsplit < 2048 && nsplit < 64 && (V / nsplit) > 4096) nsplit *= 2;
-  hipLaunchKernelGGL(sample_argmax_kernel, dim3(B, nsplit), dim3(256), 0,
-                     stream(),
-                     reinterpret_cast<unsigned long long*>(keys.data_ptr()),
-                     logits.data_ptr<float>(), temps.data_ptr<float>(),
-                     reinterpret_cast<const unsigned int*>(req_seeds.data_ptr()),
-                     reinterpret_cast<const unsigned int*>(req_pos.data_ptr()),
-                     bounds_ptr, V, (unsigned int)seed, (unsigned int)step);
+  // chunk a multiple of 8: with V % 8 == 0 every split starts on a 16-byte
+  // boundary of its row and is all vector loads
+  const int chunk = ((V + nsplit - 1) / nsplit + 7) / 8 * 8;
+  dispatch_dtype(logits, "sample_gumbel_argmax", [&]<typename T>() {
+    hipLaunchKernelGGL(
+        sample_argmax_kernel<T>, dim3(B, nsplit), dim3(256), 0, stream(),
+        reinterpret_cast<unsigned long long*>(keys.data_ptr()),
+        reinterpret_cast<const T*>(logits.data_ptr()), temps.data_ptr<float>(),
+        reinterpret_cast<const unsigned int*>(req_seeds.data_ptr()),
+        reinterpret_cast<const unsigned int*>(req_pos.data_ptr()), bounds_ptr,
+        V, logits.stride(0), chunk, (float)softcap,
+        softcap_reciprocal(softcap), (unsigned int)seed, (unsigned int)step);
+  });
   hipLaunchKernelGGL(unpack_keys_kernel, dim3((B + 255) / 256), dim3(256), 0,
                      stream(), out.data_ptr<long>(),
                      reinterpret_cast<const unsigned long long*>(keys.data_ptr()),
@@ -526,8 +566,8 @@ TORCH_LIBRARY(llmq_amd, m) {
   m.def("reshape_and_cache(Tensor key, Tensor value, Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor slot_mapping) -> ()");
   m.def("paged_decode_attention(Tensor(a!) out, Tensor q, Tensor k_cache, Tensor v_cache, Tensor block_tables, Tensor context_lens, float scale, float softcap, int window) -> ()");
   m.def("varlen_prefill_attention(Tensor(a!) out, Tensor q, Tensor k, Tensor v, Tensor cu_seqlens, Tensor cu_seqlens_k, int max_seqlen, float scale, float softcap, int window) -> ()");
-  m.def("sample_gumbel_argmax(Tensor(a!) out, Tensor(b!) keys, Tensor logits, Tensor temps, Tensor req_seeds, Tensor req_pos, int seed, int step, Tensor? bounds=None) -> ()");
-  m.def("topk_topp_bound(Tensor(a!) out_bound, Tensor logits, Tensor temps, Tensor top_ps, Tensor top_ks) -> ()");
+  m.def("sample_gumbel_argmax(Tensor(a!) out, Tensor(b!) keys, Tensor logits, Tensor temps, Tensor req_seeds, Tensor req_pos, int seed, int step, Tensor? bounds=None, float softcap=0.0) -> ()");
+  m.def("topk_topp_bound(Tensor(a!) out_bound, Tensor logits, Tensor temps, Tensor top_ps, Tensor top_ks, float softcap=0.0) -> ()");
   m.def("skinny_gemm(Tensor(a!) out, Tensor x, Tensor w, Tensor? bias, int splitk) -> ()");
   m.def("norm_add_norm(Tensor(a!) x, Tensor(b!) residual, Tensor w_post, Tensor w_pre, float eps, float offset) -> ()");
   m.def("rope_and_cache(Tensor(a!) q, Tensor(b!) k, Tensor value, Tensor(c!) k_cache, Tensor(d!) v_cache, Tensor positions, Tensor cos_sin, Tensor slot_mapping) -> ()");

@@ -203,3 +203,80 @@ __global__ void norm_add_norm_kernel(T* __restrict__ x, T* __restrict__ residual
     store16(xr + i, o);
   }
 }
+
+// Same sandwich with the row held in registers: NV 16-byte vectors per
+// thread cover hidden <= NV * 256 * 8. x and residual are loaded once, the
+// new residual stays in registers as the rounded values it is stored as, and
+// nothing written is read back; the weights are requested up front so they
+// are in flight during the first reduction. Element assignment
+// (i = tid*8 + k*256*8), per-thread summation order and both reductions are
+// those of norm_add_norm_kernel, so the outputs are bitwise the same.
+// Launch with 256 threads.
+template <typename T, int NV>
+__global__ __launch_bounds__(256) void norm_add_norm_regs_kernel(
+    T* __restrict__ x, T* __restrict__ residual, const T* __restrict__ w_post,
+    const T* __restrict__ w_pre, int hidden, float eps, float offset) {
+  constexpr int VE = Vec8<T>::kElems;
+  __shared__ float red[4];
+  const int row = blockIdx.x;
+  T* xr = x + (long)row * hidden;
+  T* rr = residual + (long)row * hidden;
+
+  Vec8<T> vx[NV], vr[NV], vwp[NV], vwn[NV];
+#pragma unroll
+  for (int k = 0; k < NV; ++k) {
+    const int i = threadIdx.x * VE + k * 256 * VE;
+    if (i < hidden) {
+      vx[k] = load16(xr + i);
+      vr[k] = load16(rr + i);
+      vwp[k] = load16(w_post + i);
+      vwn[k] = load16(w_pre + i);
+    }
+  }
+
+  float ss = 0.f;
+#pragma unroll
+  for (int k = 0; k < NV; ++k) {
+    const int i = threadIdx.x * VE + k * 256 * VE;
+    if (i < hidden) {
+#pragma unroll
+      for (int j = 0; j < VE; ++j) {
+        float f = to_f32(vx[k].data[j]);
+        ss += f * f;
+      }
+    }
+  }
+  ss = block_reduce_sum(ss, red);
+  const float inv1 = rsqrtf(ss / hidden + eps);
+
+  // residual += norm_post(x); accumulate the new residual's sumsq
+  float ss2 = 0.f;
+#pragma unroll
+  for (int k = 0; k < NV; ++k) {
+    const int i = threadIdx.x * VE + k * 256 * VE;
+    if (i < hidden) {
+#pragma unroll
+      for (int j = 0; j < VE; ++j) {
+        const float t = to_f32(vx[k].data[j]) * inv1 * (to_f32(vwp[k].data[j]) + offset);
+        const float r = to_f32(vr[k].data[j]) + t;
+        vr[k].data[j] = from_f32<T>(r);
+        ss2 += r * r;
+      }
+      store16(rr + i, vr[k]);
+    }
+  }
+  ss2 = block_reduce_sum(ss2, red);
+  const float inv2 = rsqrtf(ss2 / hidden + eps);
+
+#pragma unroll
+  for (int k = 0; k < NV; ++k) {
+    const int i = threadIdx.x * VE + k * 256 * VE;
+    if (i < hidden) {
+      Vec8<T> o;
+#pragma unroll
+      for (int j = 0; j < VE; ++j)
+        o.data[j] = from_f32<T>(to_f32(vr[k].data[j]) * inv2 * (to_f32(vwn[k].data[j]) + offset));
+      store16(xr + i, o);
+    }
+  }
+}

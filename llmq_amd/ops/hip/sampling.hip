@@ -1,7 +1,9 @@
 // Fused token sampling for gfx950.
 //
-// One pass over the fp32 logits [B, V]: each workgroup scans a vocab chunk
-// of one row and computes a local argmax of
+// One pass over the logits [B, V] as the lm_head GEMM stored them (bf16/fp16
+// or fp32): each workgroup scans a vocab chunk of one row, widens and
+// soft-caps every logit in registers (logit_value) and computes a local
+// argmax of
 //   temp <= 0:  logit                      (greedy)
 //   temp  > 0:  logit / temp + Gumbel(g)   (Gumbel-max == softmax sampling)
 // then publishes via one atomicMax on a packed (orderable-f32 | index) key.
@@ -43,27 +45,55 @@ DEVINL unsigned long long pack_key(float val, int idx) {
   return ((unsigned long long)u << 32) | (unsigned int)(~idx);
 }
 
+// Stored logit -> the fp32 value the sampler and the bound kernel work on:
+// widen, then Gemma-2's final soft-cap cap * tanh(x / cap) when softcap > 0.
+// Reproduces the eager tail `torch.tanh(logits.float() / cap) * cap` bit for
+// bit: torch divides by a host scalar as a multiply with the fp32
+// reciprocal (inv_cap = 1.0f / cap, formed on the host), tanhf is the device
+// library's function, and contraction is off so that the multiply feeding
+// tanhf is never fused into the function's first add.
+template <typename T>
+DEVINL float logit_value(T raw, float softcap, float inv_cap) {
+#pragma clang fp contract(off)
+  float x = to_f32(raw);
+  if (softcap > 0.f) {
+    x = x * inv_cap;
+    x = tanhf(x);
+    x = x * softcap;
+  }
+  return x;
+}
+
 // Per-row RNG keying: rows with a user seed (req_seeds[b] != 0) draw from
 // (request_seed, output_position) — REPRODUCIBLE for a given request
 // regardless of batch placement or engine step. Unseeded rows draw from
 // (engine seed, step, row).
+//
+// Each workgroup scans [v0, v1) = split blockIdx.y of row b: a scalar head up
+// to the first 16-byte-aligned address, 16-byte vectors (8 bf16 / 4 fp32 per
+// lane), and a scalar tail. Every logit is loaded once. A thread's indices
+// ascend (head < vectors < tail), the RNG is keyed on the element index, and
+// ties go to the lower index, so the token does not depend on alignment or
+// on the split.
+template <typename T>
 __global__ __launch_bounds__(256) void sample_argmax_kernel(
     unsigned long long* __restrict__ out_keys,  // [B], pre-zeroed
-    const float* __restrict__ logits,           // [B, V]
+    const T* __restrict__ logits,               // [B, V], row stride `stride`
     const float* __restrict__ temps,            // [B]
     const unsigned int* __restrict__ req_seeds, // [B] (0 = unseeded)
     const unsigned int* __restrict__ req_pos,   // [B] output position
     const float* __restrict__ bounds,           // [B] top-k/p keep-bound or null
-    int V, unsigned int seed, unsigned int step) {
+    int V, long stride, int chunk, float softcap, float inv_cap,
+    unsigned int seed, unsigned int step) {
+  constexpr int VE = Vec8<T>::kElems;
   const int b = blockIdx.x;
-  const int nsplit = gridDim.y;
-  const int chunk = (V + nsplit - 1) / nsplit;
   const int v0 = blockIdx.y * chunk;
+  if (v0 >= V) return;
   const int v1 = min(v0 + chunk, V);
   const float temp = temps[b];
   const bool greedy = temp <= 0.f;
   const float inv_t = greedy ? 1.0f : 1.0f / temp;
-  const float* row = logits + (long)b * V;
+  const T* row = logits + (long)b * stride;
   const unsigned int rs = req_seeds[b];
   const unsigned int kseed = rs ? rs : seed;
   const unsigned int kstep = rs ? req_pos[b] : step;
@@ -74,15 +104,27 @@ __global__ __launch_bounds__(256) void sample_argmax_kernel(
 
   float best = -3e38f;
   int best_i = v0;
-  for (int v = v0 + threadIdx.x; v < v1; v += 256) {
-    if (row[v] < bound) continue;
-    float x = row[v] * inv_t;
+  auto consider = [&](int v, T raw) {
+    const float l = logit_value(raw, softcap, inv_cap);
+    if (l < bound) return;
+    float x = l * inv_t;
     if (!greedy) {
       const float u = uniform01(kseed, kstep, kb, v);
       x += -__logf(-__logf(u));  // Gumbel(0,1)
     }
     if (x > best) { best = x; best_i = v; }
+  };
+  // elements before the first 16-byte boundary at or after row + v0
+  const int mis = (int)(((unsigned long)(row + v0) / sizeof(T)) % VE);
+  const int vb = min(v1, v0 + (mis ? VE - mis : 0));
+  const int ve = vb + (v1 - vb) / VE * VE;
+  if (v0 + (int)threadIdx.x < vb) consider(v0 + threadIdx.x, row[v0 + threadIdx.x]);
+  for (int v = vb + threadIdx.x * VE; v < ve; v += 256 * VE) {
+    const Vec8<T> vec = load16(row + v);
+#pragma unroll
+    for (int j = 0; j < VE; ++j) consider(v + j, vec.data[j]);
   }
+  if (ve + (int)threadIdx.x < v1) consider(ve + threadIdx.x, row[ve + threadIdx.x]);
   // wave reduce (value, index)
   for (int off = WAVE / 2; off > 0; off >>= 1) {
     const float ov = __shfl_xor(best, off, WAVE);
@@ -122,13 +164,14 @@ __global__ __launch_bounds__(256) void sample_argmax_kernel(
 #define TH_TPB 256
 #define TH_XMIN -32.0f
 
+template <typename T>
 __global__ __launch_bounds__(TH_TPB) void topk_topp_bound_kernel(
-    float* __restrict__ out_bound,     // [B] logit-space keep-bound
-    const float* __restrict__ logits,  // [B, V] fp32
+    float* __restrict__ out_bound,     // [B] keep-bound on logit_value()
+    const T* __restrict__ logits,      // [B, V] as stored
     const float* __restrict__ temps,   // [B]
     const float* __restrict__ top_ps,  // [B]
     const long* __restrict__ top_ks,   // [B] (0 = off)
-    int V, long stride) {
+    int V, long stride, float softcap, float inv_cap) {
   const int b = blockIdx.x;
   const int tid = threadIdx.x;
   const float T0 = temps[b];
@@ -142,7 +185,7 @@ __global__ __launch_bounds__(TH_TPB) void topk_topp_bound_kernel(
     return;
   }
   const float inv_t = 1.0f / T0;
-  const float* row = logits + (long)b * stride;
+  const T* row = logits + (long)b * stride;
 
   __shared__ float h_sum[TH_NBINS];
   __shared__ int h_cnt[TH_NBINS];
@@ -151,7 +194,8 @@ __global__ __launch_bounds__(TH_TPB) void topk_topp_bound_kernel(
 
   // ---- pass 1: row max
   float m = -3e38f;
-  for (int v = tid; v < V; v += TH_TPB) m = fmaxf(m, row[v]);
+  for (int v = tid; v < V; v += TH_TPB)
+    m = fmaxf(m, logit_value(row[v], softcap, inv_cap));
   for (int off = WAVE / 2; off > 0; off >>= 1)
     m = fmaxf(m, __shfl_xor(m, off, WAVE));
   if ((tid & (WAVE - 1)) == 0) red[tid / WAVE] = m;
@@ -183,7 +227,7 @@ __global__ __launch_bounds__(TH_TPB) void topk_topp_bound_kernel(
     const float inv_w = 1.0f / w;
     float tail = 0.f;  // mass below xlo (iter 0 only; used for Z)
     for (int v = tid; v < V; v += TH_TPB) {
-      const float x = (row[v] - m) * inv_t;
+      const float x = (logit_value(row[v], softcap, inv_cap) - m) * inv_t;
       if (x >= keep_above) continue;   // already kept (counted in p_above)
       if (x < xlo) { if (iter == 0) tail += __expf(fmaxf(x, -80.f)); continue; }
       int bin = (int)((x - xlo) * inv_w);
