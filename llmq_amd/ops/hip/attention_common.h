@@ -1,6 +1,10 @@
 // Shared device helpers for the attention kernels (prefill + decode): MFMA
-// fragment vector types, the LDS swizzle, the hidden-from-hipcc global->LDS
-// DMA with its hand-counted barriers, and the packed fp8 converter.
+// fragment vector types, the K swizzle and its S slab, the V tr16 subtile
+// image (index maps, A-fragment read, PV tile), the hidden-from-hipcc
+// global->LDS DMA with its hand-counted barriers, and the packed fp8
+// converter. Helpers are forced inline, take registers by reference and LDS
+// as pointers into the CALLER's storage: none declares a __shared__ object
+// (the pipe kernels rely on having exactly one).
 #pragma once
 
 #include "common.h"
@@ -12,6 +16,144 @@ typedef __attribute__((address_space(3))) bf16x4v lds_bf16x4;
 
 DEVINL int swz(int row, int d) {  // element-index XOR swizzle (16B granules)
   return d ^ ((row & 7) << 3);
+}
+
+// The same XOR on 16-byte granule indices, for rows of NGRAN granules (the
+// fp8 K image: glds source column and S-phase LDS column).
+DEVINL int swz_gran(int row, int c16, int ngran) {
+  return (c16 ^ (row & 7)) & (ngran - 1);
+}
+
+// S[16q, 16 keys] = Q K^T for one key slab: this lane's key row `key` of the
+// swizzled K tile `kbuf` ([keys][D] bf16), q fragments in registers
+// (frag[ks] covers dims ks*32 + kgrp*8 .. +7).
+template <int D>
+DEVINL f32x4_t attn_s_slab(const bf16x8_t (&qfrag)[D / 32], const short* kbuf,
+                           int key, int kgrp) {
+  f32x4_t s = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int ks = 0; ks < D / 32; ++ks) {
+    const int d8 = ks * 32 + kgrp * 8;
+    bf16x8_t bfrag =
+        *reinterpret_cast<const bf16x8_t*>(&kbuf[key * D + swz(key, d8)]);
+    s = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qfrag[ks], bfrag, s, 0, 0, 0);
+  }
+  return s;
+}
+
+// ---- V "tr16 subtile image" --
+// V is staged NOT as K's swizzled rows but as 32-key × 16-dim subtiles,
+// subtile st = (key/32) * (D/16) + dim/16, key quads permuted
+// (0,2,4,6,1,3,5,7) inside a subtile, so one uniform-base ds_read_b64_tr_b16
+// delivers each 16-lane group its MFMA A-fragment quad (guide T10: +11% on
+// the PV path vs scalar ds_read_u16). Subtiles are strided by 528 elements
+// (512 + 16): the unpadded 1 KB stride lands every subtile on the same banks
+// (16-way staging-write conflicts).
+constexpr int V_SUB_STRIDE = 528;
+
+constexpr int v_img_nsub(int kt, int d) { return (kt / 32) * (d / 16); }
+constexpr int v_img_elems(int kt, int d) { return v_img_nsub(kt, d) * V_SUB_STRIDE; }
+// K and V share one tile buffer: max(K rows, padded V image), in elements.
+constexpr int kv_tile_elems(int kt, int d) {
+  return kt * d > v_img_elems(kt, d) ? kt * d : v_img_elems(kt, d);
+}
+
+// Forward map: 8-element granule (key, d8) of the tile -> image element index
+// (plain staging and the fp8 convert pass write here).
+template <int D>
+constexpr int v_img_index(int key, int d8) {
+  const int dtile = d8 / 16, col0 = d8 & 15;
+  const int qq = (key & 31) >> 2;
+  const int bpos = ((qq & 1) << 2) + (qq >> 1);
+  return ((key >> 5) * (D / 16) + dtile) * V_SUB_STRIDE + bpos * 64 +
+         (key & 3) * 16 + col0;
+}
+
+// Inverse map: glds writes lane-linear, so lane `lane` of the DMA that fills
+// subtile st (elements st*V_SUB_STRIDE + lane*8 .. +7) must SOURCE this
+// (key, dim). Subtiles st..st+n of one 32-key group share `key` and step
+// `dim` by 16.
+struct VImgSrc { int key, dim; };
+template <int D>
+constexpr VImgSrc v_img_source(int st, int lane) {
+  const int ks = st / (D / 16), dtile = st % (D / 16);
+  const int pos = lane * 8;
+  const int bpos = pos / 64, rem = pos % 64;
+  const int qq = ((bpos >> 2) & 1) | ((bpos & 3) << 1);
+  return {ks * 32 + qq * 4 + rem / 16, dtile * 16 + (rem & 15)};
+}
+
+// Compile-time proof that the two maps are inverses and that the DMA covers
+// every granule of the tile exactly once.
+template <int KT, int D>
+constexpr bool v_img_maps_agree() {
+  bool seen[KT * D / 8] = {};
+  for (int st = 0; st < v_img_nsub(KT, D); ++st) {
+    for (int lane = 0; lane < WAVE; ++lane) {
+      const VImgSrc s = v_img_source<D>(st, lane);
+      if (s.key < 0 || s.key >= KT || s.dim < 0 || s.dim >= D || s.dim % 8) return false;
+      if (v_img_index<D>(s.key, s.dim) != st * V_SUB_STRIDE + lane * 8) return false;
+      bool& hit = seen[s.key * (D / 8) + s.dim / 8];
+      if (hit) return false;
+      hit = true;
+      // consecutive dim tiles of one key group: same key, dim + 16
+      if ((st + 1) % (D / 16) != 0) {
+        const VImgSrc n = v_img_source<D>(st + 1, lane);
+        if (n.key != s.key || n.dim != s.dim + 16) return false;
+      }
+    }
+  }
+  for (bool hit : seen)
+    if (!hit) return false;
+  return true;
+}
+static_assert(v_img_maps_agree<64, 64>() && v_img_maps_agree<128, 64>() &&
+              v_img_maps_agree<64, 128>() && v_img_maps_agree<128, 128>() &&
+              v_img_maps_agree<64, 256>() && v_img_maps_agree<128, 256>(),
+              "V tr16 image: forward and inverse index maps disagree");
+
+// PV A-fragment (8 keys × this lane's dim) of subtile `sub`: two transpose
+// reads — each lane reads 4 contiguous bf16 at its own 8-byte slot and the
+// hardware redistributes so lane l receives column (l&15) of its 16-lane
+// group's [4-key][16-dim] block.
+DEVINL bf16x8_t v_img_afrag(const short* img, int sub, int lane) {
+  const int e = sub * V_SUB_STRIDE + lane * 4;
+  bf16x4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)&img[e]);
+  bf16x4v hi =
+      __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)&img[e + 4 * 64]);
+  bf16x8_t a;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    a[j] = __bfloat16_as_short((__hip_bfloat16)lo[j]);
+    a[4 + j] = __bfloat16_as_short((__hip_bfloat16)hi[j]);
+  }
+  return a;
+}
+
+// OT[dims, 16q] = alpha * OT + V^T P^T over the DT 16-dim tiles from dim tile
+// `dtile0`: V from the tr16 image `img` (KT keys), P^T as b128 reads of the
+// [16 q][KT] bf16 tile `p_tile`, alpha per q row (= lane&15) from `alpha_s`.
+// rescale == false (defer-max build only) skips the alpha pass.
+template <int D, int KT, int DT>
+DEVINL void attn_pv_tile(const short* img, const short* p_tile,
+                         const float* alpha_s, bool rescale, f32x4_t (&ot)[DT],
+                         int dtile0, int lane) {
+  const int col = lane & 15, kgrp = lane >> 4;
+  const float alpha_q = rescale ? alpha_s[col] : 1.f;
+#pragma unroll
+  for (int dt = 0; dt < DT; ++dt) {
+    if (rescale) {
+      ot[dt][0] *= alpha_q; ot[dt][1] *= alpha_q;
+      ot[dt][2] *= alpha_q; ot[dt][3] *= alpha_q;
+    }
+#pragma unroll
+    for (int ks = 0; ks < KT / 32; ++ks) {
+      const bf16x8_t a = v_img_afrag(img, ks * (D / 16) + dtile0 + dt, lane);
+      const bf16x8_t b = *reinterpret_cast<const bf16x8_t*>(
+          &p_tile[col * KT + ks * 32 + kgrp * 8]);
+      ot[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, ot[dt], 0, 0, 0);
+    }
+  }
 }
 
 // 16-B-per-lane global→LDS DMA, HIDDEN from hipcc in inline asm: with the

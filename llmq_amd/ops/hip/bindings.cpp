@@ -361,6 +361,20 @@ void launch_prefill(at::Tensor& out, const at::Tensor& q, const at::Tensor& k,
                     double scale, double softcap, long window, long max_seqlen) {
   const int H = q.size(1), D = q.size(2);
   const int KVH = k.size(1);
+  // One launch for the two MFMA flash kernels and the VALU kernel (one
+  // parameter list up to the element type).
+  auto launch = [&]<typename E>(void (*kernel)(
+      E*, const E*, const E*, const E*, const int*, const int*, int, int, float,
+      float, int, long, long, long, long), dim3 grid) {
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, stream(),
+                       reinterpret_cast<E*>(out.data_ptr()),
+                       reinterpret_cast<const E*>(q.data_ptr()),
+                       reinterpret_cast<const E*>(k.data_ptr()),
+                       reinterpret_cast<const E*>(v.data_ptr()),
+                       cu.data_ptr<int>(), cu_k.data_ptr<int>(), H, KVH,
+                       (float)scale, (float)softcap, (int)window, q.stride(0),
+                       k.stride(0), v.stride(0), out.stride(0));
+  };
   if constexpr (std::is_same_v<T, __hip_bfloat16>) {
     // MFMA flash path (bf16): grid (seq, head, q-tile). Default: the glds
     // software-pipelined kernel; LLMQ_PREFILL_PIPE=0 selects the plain-
@@ -369,43 +383,16 @@ void launch_prefill(at::Tensor& out, const at::Tensor& q, const at::Tensor& k,
     dim3 fgrid(B, H, std::max(qtiles, 1));
     const char* ppe = getenv("LLMQ_PREFILL_PIPE");
     const bool use_pipe = !ppe || atoi(ppe) != 0;
-    auto lf = [&]<int HD>() {
-      if (use_pipe) {
-        hipLaunchKernelGGL((flash_prefill_pipe_kernel<HD>), fgrid, dim3(256), 0,
-                           stream(),
-                           reinterpret_cast<__hip_bfloat16*>(out.data_ptr()),
-                           reinterpret_cast<const __hip_bfloat16*>(q.data_ptr()),
-                           reinterpret_cast<const __hip_bfloat16*>(k.data_ptr()),
-                           reinterpret_cast<const __hip_bfloat16*>(v.data_ptr()),
-                           cu.data_ptr<int>(), cu_k.data_ptr<int>(), H, KVH,
-                           (float)scale, (float)softcap, (int)window,
-                           q.stride(0), k.stride(0), v.stride(0), out.stride(0));
-        return;
-      }
-      hipLaunchKernelGGL((flash_prefill_bf16_kernel<HD>), fgrid, dim3(256), 0,
-                         stream(),
-                         reinterpret_cast<__hip_bfloat16*>(out.data_ptr()),
-                         reinterpret_cast<const __hip_bfloat16*>(q.data_ptr()),
-                         reinterpret_cast<const __hip_bfloat16*>(k.data_ptr()),
-                         reinterpret_cast<const __hip_bfloat16*>(v.data_ptr()),
-                         cu.data_ptr<int>(), cu_k.data_ptr<int>(), H, KVH,
-                         (float)scale, (float)softcap, (int)window,
-                         q.stride(0), k.stride(0), v.stride(0), out.stride(0));
-    };
-    dispatch_head_dim<64, 128, 256>(D, lf);
+    dispatch_head_dim<64, 128, 256>(D, [&]<int HD>() {
+      launch.template operator()<T>(use_pipe ? flash_prefill_pipe_kernel<HD>
+                                             : flash_prefill_bf16_kernel<HD>,
+                                    fgrid);
+    });
     return;
   }
-  dim3 grid(B, H);
   dispatch_head_dim<64, 128, 256>(D, [&]<int HD>() {
-    hipLaunchKernelGGL((varlen_prefill_attention_kernel<T, HD>), grid,
-                       dim3(256), 0, stream(),
-                       reinterpret_cast<T*>(out.data_ptr()),
-                       reinterpret_cast<const T*>(q.data_ptr()),
-                       reinterpret_cast<const T*>(k.data_ptr()),
-                       reinterpret_cast<const T*>(v.data_ptr()),
-                       cu.data_ptr<int>(), cu_k.data_ptr<int>(), H, KVH,
-                       (float)scale, (float)softcap, (int)window,
-                       q.stride(0), k.stride(0), v.stride(0), out.stride(0));
+    launch.template operator()<T>(varlen_prefill_attention_kernel<T, HD>,
+                                  dim3(B, H));
   });
 }
 
@@ -455,28 +442,22 @@ void skinny_gemm(at::Tensor out, at::Tensor x, at::Tensor w,
     const char* e = getenv("LLMQ_SKG_SYNC");
     return e ? atoi(e) : 0;
   }();
-  if (z == 1) {
-    if (sync_dbg) {
-      hipLaunchKernelGGL((skinny_gemm_kernel<0, 1>), grid, dim3(SKG_NT), 0,
-                         stream(), out.data_ptr(),
-                         reinterpret_cast<const __hip_bfloat16*>(x.data_ptr()),
-                         reinterpret_cast<const __hip_bfloat16*>(w.data_ptr()),
-                         bias_ptr, M, N, K, x.stride(0), w.stride(0));
-      return;
-    }
-    hipLaunchKernelGGL((skinny_gemm_kernel<0>), grid, dim3(SKG_NT), 0, stream(),
-                       out.data_ptr(),
+  auto launch = [&](void (*kernel)(void*, const __hip_bfloat16*,
+                                   const __hip_bfloat16*, const __hip_bfloat16*,
+                                   int, int, int, long, long),
+                    void* dst, const __hip_bfloat16* bias_arg) {
+    hipLaunchKernelGGL(kernel, grid, dim3(SKG_NT), 0, stream(), dst,
                        reinterpret_cast<const __hip_bfloat16*>(x.data_ptr()),
                        reinterpret_cast<const __hip_bfloat16*>(w.data_ptr()),
-                       bias_ptr, M, N, K, x.stride(0), w.stride(0));
+                       bias_arg, M, N, K, x.stride(0), w.stride(0));
+  };
+  if (z == 1) {
+    launch(sync_dbg ? skinny_gemm_kernel<0, 1> : skinny_gemm_kernel<0>,
+           out.data_ptr(), bias_ptr);
     return;
   }
   at::Tensor slabs = at::empty({z, (long)M * N}, x.options().dtype(at::kFloat));
-  hipLaunchKernelGGL((skinny_gemm_kernel<1>), grid, dim3(SKG_NT), 0, stream(),
-                     slabs.data_ptr(),
-                     reinterpret_cast<const __hip_bfloat16*>(x.data_ptr()),
-                     reinterpret_cast<const __hip_bfloat16*>(w.data_ptr()),
-                     nullptr, M, N, K, x.stride(0), w.stride(0));
+  launch(skinny_gemm_kernel<1>, slabs.data_ptr(), nullptr);
   const long MN = (long)M * N;
   const long blocks = (MN / 4 + 255) / 256;
   hipLaunchKernelGGL(skinny_gemm_reduce_kernel, dim3(blocks), dim3(256), 0,

@@ -380,45 +380,6 @@ DEVINL bool pd_softmax_tile(const float* mpart, float* alpha_s, short* p_lds,
   return rescale;
 }
 
-// OT[dims, 16q] = alpha * OT + V^T P^T over this wave's DT 16-dim tiles,
-// V read from the tr16 subtile image `img`.
-template <int D, int PD_KT, int DT>
-DEVINL void pd_pv_tile(const short* img, const short* p_lds,
-                       const float* alpha_s, bool rescale, f32x4_t (&ot)[DT],
-                       int wid, int lane) {
-  const int col = lane & 15, kgrp = lane >> 4;
-  const float alpha_q = rescale ? alpha_s[col] : 1.f;
-#pragma unroll
-  for (int dt = 0; dt < DT; ++dt) {
-    if (rescale) {
-      ot[dt][0] *= alpha_q; ot[dt][1] *= alpha_q;
-      ot[dt][2] *= alpha_q; ot[dt][3] *= alpha_q;
-    }
-    const int dtile = wid * DT + dt;
-#pragma unroll
-    for (int ks = 0; ks < PD_KT / 32; ++ks) {
-      // two transpose reads give the full 8-key A-fragment: each lane
-      // reads 4 contiguous bf16 at its own 8-byte slot and the hardware
-      // redistributes so lane l receives column (l&15) of its 16-lane
-      // group's [4-key][16-dim] block
-      const int sub = (ks * (D / 16) + dtile) * 528 + lane * 4;
-      bf16x4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
-          (lds_bf16x4*)&img[sub]);
-      bf16x4v hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
-          (lds_bf16x4*)&img[sub + 4 * 64]);
-      bf16x8_t a;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        a[j] = __bfloat16_as_short((__hip_bfloat16)lo[j]);
-        a[4 + j] = __bfloat16_as_short((__hip_bfloat16)hi[j]);
-      }
-      bf16x8_t bb = *reinterpret_cast<const bf16x8_t*>(
-          &p_lds[col * PD_KT + ks * 32 + kgrp * 8]);
-      ot[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, bb, ot[dt], 0, 0, 0);
-    }
-  }
-}
-
 // Epilogue after the per-slab l partials are visible in l_part: sum l, then
 // either (gridDim.z > 1) write this z-block's UNNORMALISED fp32 partial rows
 // and their (m, l) stats to scratch, or normalise and store bf16 to out.
@@ -516,12 +477,7 @@ __global__ __launch_bounds__(NW * WAVE) void paged_decode_mfma_kernel(
   const int col = lane & 15;   // MFMA col lane (key for S, qrow for OT)
   const int kgrp = lane >> 4;  // 0..3
 
-  // V's tr-subtile image strides subtiles by 528 elems (512 + 16): the
-  // unpadded 1 KB stride lands every subtile on the same banks (16-way
-  // staging-write conflicts). Sized for max(K rows, padded V image).
-  constexpr int NSUB = (PD_KT / 32) * (D / 16);
-  constexpr int KV_ELEMS = (PD_KT * D > NSUB * 528) ? PD_KT * D : NSUB * 528;
-  __shared__ __attribute__((aligned(16))) short kv_lds[KV_ELEMS];  // K then V
+  __shared__ __attribute__((aligned(16))) short kv_lds[kv_tile_elems(PD_KT, D)];  // K then V
   __shared__ __attribute__((aligned(16))) short p_lds[16 * PD_KT];  // [qrow][key]
   __shared__ float mpart_lds[NW][16];  // per-wave row-max partials
   __shared__ float alpha_lds[16];      // per-row rescale for the OT lanes
@@ -581,17 +537,7 @@ __global__ __launch_bounds__(NW * WAVE) void paged_decode_mfma_kernel(
     __syncthreads();
 
     // ---- S[16, 16] for this wave's key slab
-    f32x4_t s = {0.f, 0.f, 0.f, 0.f};
-    {
-      const int key = wid * 16 + col;
-#pragma unroll
-      for (int ks = 0; ks < KS; ++ks) {
-        const int d8 = ks * 32 + kgrp * 8;
-        bf16x8_t bfrag =
-            *reinterpret_cast<const bf16x8_t*>(&kv_lds[key * D + swz(key, d8)]);
-        s = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qfrag[ks], bfrag, s, 0, 0, 0);
-      }
-    }
+    const f32x4_t s = attn_s_slab<D>(qfrag, kv_lds, wid * 16 + col, kgrp);
     // scale, softcap, bounds mask; rows r = kgrp*4 + reg
     float sv[NREG], mx[NREG];
     pd_scale_mask_rowmax<NREG>(s, base + wid * 16 + col, L, start, scale, softcap,
@@ -603,18 +549,11 @@ __global__ __launch_bounds__(NW * WAVE) void paged_decode_mfma_kernel(
     __syncthreads();  // mparts ready; every wave is past its K reads
 
     // ---- stage V into the SAME buffer; its latency hides under softmax VALU.
-    // V uses a tr-read subtile image (NOT K's swizzled rows): 32-key × 16-dim
-    // subtiles, key-quads permuted (0,2,4,6,1,3,5,7) so one uniform-base
-    // ds_read_b64_tr_b16 delivers each 16-lane group its MFMA A-fragment
-    // quad (guide T10: +11% on the PV path vs scalar ds_read_u16).
+    // V uses the tr16 subtile image (NOT K's swizzled rows).
     for (int c = tid; c < NCK; c += NT) {
       const int key = c / CPK;
       const int d8 = (c % CPK) * 8;
-      const int dt = d8 / 16, col0 = d8 & 15;
-      const int qq = (key & 31) >> 2;
-      const int block_pos = ((qq & 1) << 2) + (qq >> 1);
-      const int dst = ((key >> 5) * (D / 16) + dt) * 528 + block_pos * 64 +
-                      (key & 3) * 16 + col0;
+      const int dst = v_img_index<D>(key, d8);
       const int gkey = base + key;
       if (gkey < L) {
         const int bidx = gkey >> bs_shift;
@@ -653,7 +592,7 @@ __global__ __launch_bounds__(NW * WAVE) void paged_decode_mfma_kernel(
     __syncthreads();  // V + P + alpha ready
 
     // ---- OT[dims, 16q] += V^T P^T over this wave's dim slab
-    pd_pv_tile<D, PD_KT, DT>(kv_lds, p_lds, alpha_lds, true, ot, wid, lane);
+    attn_pv_tile<D, PD_KT, DT>(kv_lds, p_lds, alpha_lds, true, ot, wid * DT, lane);
     __syncthreads();  // V/P consumed; next chunk may overwrite
   }
 
@@ -687,8 +626,9 @@ __global__ __launch_bounds__(NW * WAVE) void paged_decode_mfma_kernel(
 //     vmcnt(NI_K) (V landed, K still streaming); the loop-top barrier waits
 //     vmcnt(0) (K landed). A `__syncthreads()` would drain the glds queue
 //     at every barrier (the documented HIP-compiler ceiling).
-//   - The chunk containing L falls back to plain staged writes (glds cannot
-//     zero-fill; garbage V rows would reach the PV MFMA as NaN×0).
+//   - glds cannot zero-fill, so keys past L (the chunk containing L) clamp
+//     their source to cache row L-1: finite real data, masked in S and
+//     carrying P == 0 into PV. Every chunk stays on the pipeline.
 // Per-workgroup timeline: the only window with no HBM traffic in flight is
 // the S phase (~hundreds of cycles vs ~6 µs of stream per chunk).
 
@@ -716,9 +656,9 @@ __global__ __launch_bounds__(NW * WAVE, (PD_KT <= 64 ? 4 : 2)) void paged_decode
   constexpr int DT = D4 / 16;       // 16-dim MFMA tiles per wave
   constexpr int CPK = D / 8;        // 16B granules per key row
   constexpr int NI_K = PD_KT * CPK / NT;          // K glds per wave per chunk
-  constexpr int NSUB = (PD_KT / 32) * (D / 16);   // V tr-subtiles per chunk
+  constexpr int NSUB = v_img_nsub(PD_KT, D);      // V tr-subtiles per chunk
   constexpr int NI_V = NSUB / NW;                 // V glds per wave per chunk
-  constexpr int KV_ELEMS = (PD_KT * D > NSUB * 528) ? PD_KT * D : NSUB * 528;
+  constexpr int KV_ELEMS = kv_tile_elems(PD_KT, D);
   static_assert(PD_KT % 32 == 0 && SLABS <= NW && NSUB % NW == 0, "");
   static_assert(PD_KT * CPK % NT == 0 && D % NW == 0 && D4 % 16 == 0, "");
 
@@ -813,15 +753,10 @@ __global__ __launch_bounds__(NW * WAVE, (PD_KT <= 64 ? 4 : 2)) void paged_decode
   };
   // V: subtile st, in-subtile granule = lane (tr16 image inverse mapping).
   auto v_src = [&](int base, int st) -> const __hip_bfloat16* {
-    const int ks = st / (D / 16), dtile = st % (D / 16);
-    const int pos = lane * 8;
-    const int bpos = pos / 64, rem = pos % 64;
-    const int qq = ((bpos >> 2) & 1) | ((bpos & 3) << 1);
-    const int key = ks * 32 + qq * 4 + rem / 16;
-    const int dim = dtile * 16 + (rem & 15);
-    const int gkey = min(base + key, L - 1);
+    const VImgSrc s = v_img_source<D>(st, lane);
+    const int gkey = min(base + s.key, L - 1);
     const long blk = bt_l[gkey >> bs_shift];
-    return v_cache + head_off + blk * blk_stride + ((gkey & bs_mask) * D + dim);
+    return v_cache + head_off + blk * blk_stride + ((gkey & bs_mask) * D + s.dim);
   };
 
   // All source addresses first, then the DMAs back to back: glds16 is an
@@ -839,13 +774,15 @@ __global__ __launch_bounds__(NW * WAVE, (PD_KT <= 64 ? 4 : 2)) void paged_decode
   };
   // A wave's NI_V subtiles are consecutive 16-dim tiles of ONE 32-key group,
   // so its lanes read the same cache row for all of them: one row address
-  // per chunk, then a 16-element step per subtile.
+  // per chunk, then a 16-element step per subtile (v_img_source's key/dim
+  // progression, part of the compile-time layout check).
   static_assert((D / 16) % NI_V == 0, "a wave's V subtiles share their keys");
   auto issue_v = [&](int base, short* dst) {
     const __hip_bfloat16* const row = v_src(base, wid * NI_V);
 #pragma unroll
     for (int j = 0; j < NI_V; ++j) {
-      const int off = __builtin_amdgcn_readfirstlane((wid * NI_V + j) * 528);
+      const int off =
+          __builtin_amdgcn_readfirstlane((wid * NI_V + j) * V_SUB_STRIDE);
       glds16(row + j * 16, dst + off);
     }
   };
@@ -862,15 +799,8 @@ __global__ __launch_bounds__(NW * WAVE, (PD_KT <= 64 ? 4 : 2)) void paged_decode
     // ---- S[16,16] for this wave's slab
     float sv[NREG];
     if (s_wave) {
-      f32x4_t s = {0.f, 0.f, 0.f, 0.f};
       const int key = slab * 16 + col;
-#pragma unroll
-      for (int ks = 0; ks < KS; ++ks) {
-        const int d8 = ks * 32 + kgrp * 8;
-        bf16x8_t bfrag =
-            *reinterpret_cast<const bf16x8_t*>(&X[key * D + swz(key, d8)]);
-        s = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qfrag[ks], bfrag, s, 0, 0, 0);
-      }
+      const f32x4_t s = attn_s_slab<D>(qfrag, X, key, kgrp);
       float mx[NREG];
       pd_scale_mask_rowmax<NREG>(s, base + key, L, start, scale, softcap, sv, mx);
       if (col == 0 && wid < SLABS) {
@@ -898,7 +828,7 @@ __global__ __launch_bounds__(NW * WAVE, (PD_KT <= 64 ? 4 : 2)) void paged_decode
     }
 
     // ---- OT[dims,16q] += V^T P^T over this wave's dim slab
-    pd_pv_tile<D, PD_KT, DT>(X, p_lds2, alpha_s, rescale, ot, wid, lane);
+    attn_pv_tile<D, PD_KT, DT>(X, p_lds2, alpha_s, rescale, ot, wid * DT, lane);
     // No trailing barrier: the next loop-top barrier (vmcnt(0)) both
     // protects X against the glds of chunk base+2 (issued only after the
     // NEXT post-S barrier) and confirms K(next) landed in Y.
@@ -954,8 +884,7 @@ __global__ __launch_bounds__(NW * WAVE, 4) void paged_decode_pipe_fp8_kernel(
   constexpr int G16B = D / 16;          // 16B granules per fp8 key row
   constexpr int NI_K = PD_KT * G16B / NT;   // fp8-K glds per wave
   constexpr int NI_VR = NI_K;               // raw fp8-V glds per wave
-  constexpr int NSUB = (PD_KT / 32) * (D / 16);
-  constexpr int IMG_ELEMS = NSUB * 528;     // bf16 tr16 image (shorts)
+  constexpr int IMG_ELEMS = v_img_elems(PD_KT, D);  // bf16 tr16 image (shorts)
   constexpr int RAW_BYTES = PD_KT * D;      // fp8 K front == raw V size
   static_assert(IMG_ELEMS * 2 >= 2 * RAW_BYTES,
                 "image must cover K-front + V-raw back");
@@ -1044,7 +973,7 @@ __global__ __launch_bounds__(NW * WAVE, 4) void paged_decode_pipe_fp8_kernel(
       const int g = (wid * NI_K + j) * 64 + lane;  // 16B granule
       const int key = g / G16B;
       const int c16 = g % G16B;
-      const int src_col = ((c16 ^ (key & 7)) & (G16B - 1)) << 4;
+      const int src_col = swz_gran(key, c16, G16B) << 4;
       src[j] = kv_row(base + key, k_cache) + src_col;
     }
 #pragma unroll
@@ -1089,8 +1018,7 @@ __global__ __launch_bounds__(NW * WAVE, 4) void paged_decode_pipe_fp8_kernel(
 #pragma unroll
       for (int ks = 0; ks < KS; ++ks) {
         const int d8 = ks * 32 + kgrp * 8;
-        const int c16 = d8 >> 4;
-        const int lds_col = ((c16 ^ (key & 7)) & (G16B - 1)) * 16 + (d8 & 15);
+        const int lds_col = swz_gran(key, d8 >> 4, G16B) * 16 + (d8 & 15);
         const uint2 raw = *reinterpret_cast<const uint2*>(krow + lds_col);
         const bf16x8_t bfrag = fp8x8_to_bf16(raw.x, raw.y);
         s = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qfrag[ks], bfrag, s, 0, 0, 0);
@@ -1133,19 +1061,15 @@ __global__ __launch_bounds__(NW * WAVE, 4) void paged_decode_pipe_fp8_kernel(
         const int c = tid + j * NT;
         const int key = c / CPK;
         const int d8 = (c % CPK) * 8;
-        const int dtile = d8 / 16, col0 = d8 & 15;
-        const int qq = (key & 31) >> 2;
-        const int bpos = ((qq & 1) << 2) + (qq >> 1);
-        const int pdst = ((key >> 5) * (D / 16) + dtile) * 528 + bpos * 64 +
-                         (key & 3) * 16 + col0;
         const uint2 rr = *reinterpret_cast<const uint2*>(raw + key * D + d8);
-        *reinterpret_cast<bf16x8_t*>(&X[pdst]) = fp8x8_to_bf16(rr.x, rr.y);
+        *reinterpret_cast<bf16x8_t*>(&X[v_img_index<D>(key, d8)]) =
+            fp8x8_to_bf16(rr.x, rr.y);
       }
     }
     pipe_barrier();  // image + P + alpha visible
 
     // ---- PV from the bf16 tr16 image
-    pd_pv_tile<D, PD_KT, DT>(X, p_lds2, alpha_s, rescale, ot, wid, lane);
+    attn_pv_tile<D, PD_KT, DT>(X, p_lds2, alpha_s, rescale, ot, wid * DT, lane);
     // next loop-top barrier (vm0) protects X/Y rotation
   }
 
