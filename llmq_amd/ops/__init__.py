@@ -225,6 +225,12 @@ def varlen_prefill_attention(
 # ---------------------------------------------------------- skinny GEMM --
 
 
+def _skg_stageable(t: torch.Tensor) -> bool:
+    """The binding's preconditions on a skinny_gemm operand (x or w)."""
+    return (t.stride(-1) == 1 and t.stride(0) % 8 == 0
+            and t.data_ptr() % 16 == 0)
+
+
 def skinny_gemm(
     x: torch.Tensor,          # [M, K] bf16
     w: torch.Tensor,          # [N, K] bf16 (torch linear weight layout)
@@ -236,14 +242,23 @@ def skinny_gemm(
 
     256x256x64 MFMA tile, glds-staged with source-side st_16x32 swizzle,
     counted-vmcnt pipeline; split-K slabs + fused reduce for narrow-N
-    shapes. Falls back to F.linear off-GPU / unsupported shapes."""
+    shapes. Falls back to F.linear off-GPU / unsupported shapes, and for
+    views the 16-byte staging loads cannot take: x and w need a 16-byte
+    aligned base, unit inner stride and a row stride that is a multiple of
+    8 elements; bias must be contiguous."""
     M, K = x.shape
     N = w.shape[0]
     if not (x.is_cuda and x.dtype == torch.bfloat16 and K % 64 == 0
-            and N % 4 == 0 and has_hip_ext()):
+            and N % 4 == 0 and M > 0 and K > 0 and N > 0
+            and _skg_stageable(x) and _skg_stageable(w)
+            and (bias is None or bias.is_contiguous()) and has_hip_ext()):
         import torch.nn.functional as F
 
-        return F.linear(x, w, bias)
+        out_ref = F.linear(x, w, bias)
+        if out is None:
+            return out_ref
+        out.copy_(out_ref)
+        return out
     if out is None:
         out = torch.empty(M, N, dtype=torch.bfloat16, device=x.device)
     _EXT.skinny_gemm(out, x, w, bias, splitk)

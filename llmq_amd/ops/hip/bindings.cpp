@@ -417,31 +417,50 @@ void varlen_prefill_attention(at::Tensor out, at::Tensor q, at::Tensor k,
 void skinny_gemm(at::Tensor out, at::Tensor x, at::Tensor w,
                  c10::optional<at::Tensor> bias, long splitk) {
   CHECK_GPU(x);
+  CHECK_GPU(w);
+  CHECK_GPU(out);
+  TORCH_CHECK(x.dim() == 2 && w.dim() == 2 && out.dim() == 2);
   CHECK_LASTDIM(x);
   CHECK_LASTDIM(w);
   TORCH_CHECK(x.scalar_type() == at::kBFloat16 && w.scalar_type() == at::kBFloat16);
   TORCH_CHECK(out.scalar_type() == at::kBFloat16 && out.is_contiguous());
   const int M = x.size(0), K = x.size(1), N = w.size(0);
   TORCH_CHECK(w.size(1) == K && out.size(0) == M && out.size(1) == N);
+  TORCH_CHECK(M > 0 && N > 0 && K > 0);
   TORCH_CHECK(K % SKG_BK == 0, "K must be a multiple of 64");
   TORCH_CHECK(N % 4 == 0, "N must be a multiple of 4");
+  // Staging moves 16-byte granules from src + row * stride + col (col a
+  // multiple of 8 elements): base and row pitch must keep them aligned.
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0 &&
+                  reinterpret_cast<uintptr_t>(w.data_ptr()) % 16 == 0,
+              "x and w must be 16-byte aligned");
+  TORCH_CHECK(x.stride(0) % 8 == 0 && w.stride(0) % 8 == 0,
+              "x and w row strides must be multiples of 8 elements");
+  TORCH_CHECK(splitk >= 0, "splitk must be >= 0 (0 = auto)");
   const __hip_bfloat16* bias_ptr = nullptr;
   if (bias.has_value() && bias->defined()) {
+    CHECK_GPU((*bias));
     TORCH_CHECK(bias->scalar_type() == at::kBFloat16 && bias->numel() == N);
+    TORCH_CHECK(bias->is_contiguous(), "bias must be contiguous");
     bias_ptr = reinterpret_cast<const __hip_bfloat16*>(bias->data_ptr());
   }
   const int mt = (M + SKG_BM - 1) / SKG_BM;
   const int nt = (N + SKG_BN - 1) / SKG_BN;
+  const int ksteps = K / SKG_BK;
   int z = (int)splitk;
   if (z <= 0) {  // auto: fill the chip (>=256 blocks), keep >=8 K-steps/slice
     z = 1;
-    while (mt * nt * z < 256 && (K / SKG_BK) / (z * 2) >= 8 && z < 8) z *= 2;
+    while (mt * nt * z < 256 && ksteps / (z * 2) >= 8 && z < 8) z *= 2;
   }
+  // The kernel gives each slice per = ceil(ksteps / z) steps; drop the
+  // slices that rule leaves empty, so the reduce only reads written slabs.
+  const int per = (ksteps + z - 1) / z;
+  z = (ksteps + per - 1) / per;
   dim3 grid(mt, nt, z);
-  static const int sync_dbg = [] {
-    const char* e = getenv("LLMQ_SKG_SYNC");
-    return e ? atoi(e) : 0;
-  }();
+  // Debug staging (plain loads + __syncthreads instead of the glds
+  // pipeline). Read per call, like LLMQ_DECODE_PIPE.
+  const char* sync_env = getenv("LLMQ_SKG_SYNC");
+  const bool sync_dbg = sync_env && atoi(sync_env) != 0;
   auto launch = [&](void (*kernel)(void*, const __hip_bfloat16*,
                                    const __hip_bfloat16*, const __hip_bfloat16*,
                                    int, int, int, long, long),
@@ -457,7 +476,8 @@ void skinny_gemm(at::Tensor out, at::Tensor x, at::Tensor w,
     return;
   }
   at::Tensor slabs = at::empty({z, (long)M * N}, x.options().dtype(at::kFloat));
-  launch(skinny_gemm_kernel<1>, slabs.data_ptr(), nullptr);
+  launch(sync_dbg ? skinny_gemm_kernel<1, 1> : skinny_gemm_kernel<1>,
+         slabs.data_ptr(), nullptr);
   const long MN = (long)M * N;
   const long blocks = (MN / 4 + 255) / 256;
   hipLaunchKernelGGL(skinny_gemm_reduce_kernel, dim3(blocks), dim3(256), 0,
