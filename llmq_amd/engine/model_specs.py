@@ -1,4 +1,4 @@
-"""Model architecture specs for the Llama/Qwen2/Gemma-2 families.
+"""Model architecture specs for the Llama/Qwen2/Qwen3/Gemma-2 families.
 
 The reference serves Tower-Plus-{2B,9B,72B}, Llama-3.2 and Gemma-2 via vLLM
 (README.md:98-108,169). All of those are decoder-only
@@ -6,6 +6,7 @@ RMSNorm+RoPE+GQA transformers differing in a handful of switches, captured
 here as one ModelSpec:
 
   qkv_bias          Qwen2 adds bias to q/k/v projections
+  qk_norm           Qwen3 RMS-norms q and k per head (over head_dim) before RoPE
   tied_embeddings   small models tie lm_head to the embedding
   gelu              Gemma uses GeGLU (gelu_tanh) instead of SiLU
   post_norms        Gemma-2 adds post-attention/post-mlp norms
@@ -31,7 +32,7 @@ from typing import Optional
 @dataclass
 class ModelSpec:
     name: str
-    family: str  # "llama" | "qwen2" | "gemma2"
+    family: str  # "llama" | "mistral" | "qwen2" | "qwen3" | "gemma2"
     vocab_size: int
     hidden_size: int
     intermediate_size: int
@@ -43,6 +44,7 @@ class ModelSpec:
     rope_theta: float = 10000.0
     max_position_embeddings: int = 8192
     qkv_bias: bool = False
+    qk_norm: bool = False
     tied_embeddings: bool = False
     gelu: bool = False
     post_norms: bool = False
@@ -87,6 +89,8 @@ class ModelSpec:
         )
         if self.post_norms:
             per_layer += 2 * self.hidden_size
+        if self.qk_norm:
+            per_layer += 2 * self.head_dim
         total = embed + self.num_layers * per_layer + self.hidden_size
         if not self.tied_embeddings:
             total += embed
@@ -108,6 +112,19 @@ def _qwen2(name, vocab, hidden, inter, layers, heads, kv_heads, head_dim=None, *
         intermediate_size=inter, num_layers=layers, num_heads=heads,
         num_kv_heads=kv_heads, head_dim=head_dim or hidden // heads, rms_eps=1e-6,
         rope_theta=1000000.0, qkv_bias=True, **kw,
+    )
+
+
+def _qwen3(name, hidden, inter, layers, heads, head_dim=128, **kw):
+    kw.setdefault("vocab_size", 151936)
+    kw.setdefault("num_kv_heads", 8)
+    kw.setdefault("max_position_embeddings", 40960)
+    kw.setdefault("eos_token_id", 151645)
+    kw.setdefault("bos_token_id", 151643)
+    return ModelSpec(
+        name=name, family="qwen3", hidden_size=hidden, intermediate_size=inter,
+        num_layers=layers, num_heads=heads, head_dim=head_dim, rms_eps=1e-6,
+        rope_theta=1000000.0, qk_norm=True, **kw,
     )
 
 
@@ -144,6 +161,10 @@ PRESETS = {
                               max_position_embeddings=512, tied_embeddings=True),
     "tiny-qwen2": _qwen2("tiny-qwen2", 512, 64, 128, 2, 4, 2, head_dim=64,
                          max_position_embeddings=512, tied_embeddings=True),
+    "tiny-qwen3": _qwen3("tiny-qwen3", 64, 128, 2, 4, head_dim=64,
+                         vocab_size=512, num_kv_heads=2,
+                         max_position_embeddings=512, tied_embeddings=True,
+                         eos_token_id=2, bos_token_id=1),
     "tiny-gemma2": _gemma2("tiny-gemma2", 512, 64, 128, 2, 4, 2, 64,
                            sliding_window=64, max_position_embeddings=512),
     # Llama 3.2 (vocab 128256, rope theta 500k)
@@ -170,6 +191,14 @@ PRESETS = {
     "qwen2.5-32b": _qwen2("qwen2.5-32b", 152064, 5120, 27648, 64, 40, 8,
                           max_position_embeddings=32768,
                           eos_token_id=151645, bos_token_id=151643),
+    # Qwen3 dense (Qwen2 layout without qkv bias, explicit head_dim 128,
+    # per-head q/k RMSNorm before RoPE)
+    "qwen3-0.6b": _qwen3("qwen3-0.6b", 1024, 3072, 28, 16, tied_embeddings=True),
+    "qwen3-1.7b": _qwen3("qwen3-1.7b", 2048, 6144, 28, 16, tied_embeddings=True),
+    "qwen3-4b": _qwen3("qwen3-4b", 2560, 9728, 36, 32, tied_embeddings=True),
+    "qwen3-8b": _qwen3("qwen3-8b", 4096, 12288, 36, 32),
+    "qwen3-14b": _qwen3("qwen3-14b", 5120, 17408, 40, 40),
+    "qwen3-32b": _qwen3("qwen3-32b", 5120, 25600, 64, 64),
     # Llama-3.1-8B / 70B (same layout; 70B pairs with TP=8 or fits 1 GPU)
     "llama-3.1-8b": _llama("llama-3.1-8b", 128256, 4096, 14336, 32, 32, 8,
                            head_dim=128, rope_theta=500000.0,
@@ -215,6 +244,8 @@ ALIASES = {
     "meta-llama/llama-3.1-70b-instruct": "llama-3.1-70b",
     "llama-3.1-70b-instruct": "llama-3.1-70b",
     "qwen/qwen2.5-32b-instruct": "qwen2.5-32b",
+    **{f"qwen/qwen3-{size}": f"qwen3-{size}"
+       for size in ("0.6b", "1.7b", "4b", "8b", "14b", "32b")},
 }
 
 
@@ -224,8 +255,19 @@ def spec_from_hf_config(path: Path, name: str) -> ModelSpec:
         cfg = json.load(fh)
     arch = (cfg.get("architectures") or [""])[0].lower()
     model_type = cfg.get("model_type", "").lower()
+    if "qwen3moe" in arch or "qwen3_moe" in model_type:
+        raise ValueError(
+            f"{name}: Qwen3-MoE ({model_type or arch}) is not supported; "
+            "only the dense Qwen3 models are")
     if "gemma2" in arch or model_type == "gemma2":
         family = "gemma2"
+    elif "qwen3" in arch or model_type == "qwen3":
+        family = "qwen3"
+        if cfg.get("use_sliding_window"):
+            raise ValueError(
+                f"{name}: Qwen3 with use_sliding_window=true is not supported "
+                "(no released dense Qwen3 sets it; the windowed-layer pattern "
+                "would have to be guessed)")
     elif "qwen2" in arch or model_type == "qwen2":
         family = "qwen2"
     elif "mistral" in arch or model_type == "mistral":
@@ -256,7 +298,9 @@ def spec_from_hf_config(path: Path, name: str) -> ModelSpec:
         rope_theta=rope_theta,
         rope_scaling=rope_scaling,
         max_position_embeddings=cfg.get("max_position_embeddings", 8192),
-        qkv_bias=family == "qwen2",
+        qkv_bias=(bool(cfg.get("attention_bias", False)) if family == "qwen3"
+                  else family == "qwen2"),
+        qk_norm=family == "qwen3",
         tied_embeddings=cfg.get("tie_word_embeddings", False),
         gelu=family == "gemma2",
         post_norms=family == "gemma2",

@@ -1,4 +1,5 @@
-"""Decoder-only transformer covering the Llama / Qwen2 / Gemma-2 families.
+"""Decoder-only transformer covering the Llama / Mistral / Qwen2 / Qwen3 /
+Gemma-2 families.
 
 One functional implementation driven by ModelSpec switches (SURVEY §2.9:
 the model set the reference serves through vLLM). Design notes, MI355X-first:
@@ -8,7 +9,8 @@ the model set the reference serves through vLLM). Design notes, MI355X-first:
   larger hipBLASLt GEMMs (xGMI-budgeted TP shards stay big).
 - Hot elementwise/normalisation ops go through llmq_amd.ops → hand-written
   CDNA4 kernels on GPU (fused residual+RMSNorm, fused RoPE q‖k, fused
-  SiLU·mul / GeGLU, paged attention, KV scatter).
+  SiLU·mul / GeGLU, paged attention, KV scatter; Qwen3's per-head q/k norm
+  is fused into the RoPE + cache-write launch).
 - Tensor parallelism: column-shard qkv & gate_up, row-shard o & down with a
   single RCCL all-reduce after each of the two row GEMMs per layer (the
   standard 2-allreduce/layer Megatron split; over 7×153 GB/s xGMI links the
@@ -48,7 +50,7 @@ def _proj(x: torch.Tensor, w: torch.Tensor, bias=None) -> torch.Tensor:
 
 class LayerWeights:
     __slots__ = (
-        "input_norm", "qkv", "qkv_bias", "o", "post_attn_norm",
+        "input_norm", "qkv", "qkv_bias", "q_norm", "k_norm", "o", "post_attn_norm",
         "pre_mlp_norm", "gate_up", "down", "post_mlp_norm",
     )
 
@@ -56,6 +58,8 @@ class LayerWeights:
         self.input_norm = None
         self.qkv = None
         self.qkv_bias = None
+        self.q_norm = None
+        self.k_norm = None
         self.o = None
         self.post_attn_norm = None
         self.pre_mlp_norm = None
@@ -123,6 +127,9 @@ class CausalLM:
             lw.qkv = self._empty(self.q_size + 2 * self.kv_size, s.hidden_size)
             if s.qkv_bias:
                 lw.qkv_bias = self._empty(self.q_size + 2 * self.kv_size)
+            if s.qk_norm:
+                lw.q_norm = self._empty(s.head_dim)
+                lw.k_norm = self._empty(s.head_dim)
             lw.o = self._empty(s.hidden_size, self.q_size)
             lw.pre_mlp_norm = self._empty(s.hidden_size)
             lw.gate_up = self._empty(2 * self.inter, s.hidden_size)
@@ -166,6 +173,9 @@ class CausalLM:
             fill(lw.qkv, std)
             if lw.qkv_bias is not None:
                 lw.qkv_bias.zero_()
+            if lw.q_norm is not None:
+                lw.q_norm.fill_(1.0)
+                lw.k_norm.fill_(1.0)
             fill(lw.o, out_std)
             lw.pre_mlp_norm.fill_(1.0 - self.norm_offset)
             fill(lw.gate_up, std)
@@ -187,6 +197,9 @@ class CausalLM:
             out[p + "qkv"] = lw.qkv
             if lw.qkv_bias is not None:
                 out[p + "qkv_bias"] = lw.qkv_bias
+            if lw.q_norm is not None:
+                out[p + "q_norm"] = lw.q_norm
+                out[p + "k_norm"] = lw.k_norm
             out[p + "o"] = lw.o
             out[p + "pre_mlp_norm"] = lw.pre_mlp_norm
             out[p + "gate_up"] = lw.gate_up
@@ -254,10 +267,17 @@ class CausalLM:
             q = q.view(T, self.heads, s.head_dim)
             k = k.view(T, self.kv_heads, s.head_dim)
             v = v.view(T, self.kv_heads, s.head_dim)
-            ops.rope_and_cache(
-                q, k, v, kv_cache.k[i], kv_cache.v[i], positions,
-                self.rope_cache, meta.slot_mapping,
-            )
+            if s.qk_norm:
+                ops.qknorm_rope_and_cache(
+                    q, k, v, kv_cache.k[i], kv_cache.v[i], lw.q_norm,
+                    lw.k_norm, s.rms_eps, 0.0, positions, self.rope_cache,
+                    meta.slot_mapping,
+                )
+            else:
+                ops.rope_and_cache(
+                    q, k, v, kv_cache.k[i], kv_cache.v[i], positions,
+                    self.rope_cache, meta.slot_mapping,
+                )
             window = s.sliding_window if s.layer_uses_sliding_window(i) else 0
             if meta.is_prefill:
                 attn = self._prefill_attn(q, k, v, meta, kv_cache, i, window)

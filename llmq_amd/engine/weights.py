@@ -2,7 +2,7 @@
 
 Reference counterpart: vLLM's weight loader, consumed implicitly through
 AsyncLLMEngine.from_engine_args (vllm_worker.py:105-123). Handles the
-Llama/Qwen2/Gemma-2 HF naming and packs q/k/v and gate/up into the fused
+Llama/Qwen2/Qwen3/Gemma-2 HF naming and packs q/k/v and gate/up into the fused
 GEMM tensors. Tensor-parallel loads take each rank's shard only.
 """
 
@@ -75,6 +75,10 @@ def load_safetensors_weights(model, path: Path) -> None:
             kb = _shard_rows(get(p + "self_attn.k_proj.bias"), rank, size)
             vb = _shard_rows(get(p + "self_attn.v_proj.bias"), rank, size)
             copy_(lw.qkv_bias, torch.cat([qb, kb, vb], dim=0))
+        if spec.qk_norm:
+            # per-head-dim, shared by all heads: every TP rank takes them whole
+            copy_(lw.q_norm, get(p + "self_attn.q_norm.weight"))
+            copy_(lw.k_norm, get(p + "self_attn.k_norm.weight"))
         copy_(lw.o, _shard_cols(get(p + "self_attn.o_proj.weight"), rank, size))
         gate = _shard_rows(get(p + "mlp.gate_proj.weight"), rank, size)
         up = _shard_rows(get(p + "mlp.up_proj.weight"), rank, size)

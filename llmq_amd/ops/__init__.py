@@ -156,6 +156,36 @@ def rope_and_cache(
     torch_ref.reshape_and_cache(k, v, k_cache, v_cache, slot_mapping)
 
 
+_QKNORM_HEAD_DIMS = (64, 128, 256)  # qknorm_rope_and_cache_kernel's envelope
+
+
+def qknorm_rope_and_cache(
+    q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
+    k_cache: torch.Tensor, v_cache: torch.Tensor,
+    q_weight: torch.Tensor, k_weight: torch.Tensor, eps: float, offset: float,
+    positions: torch.Tensor, cos_sin: torch.Tensor, slot_mapping: torch.Tensor,
+) -> None:
+    """Qwen3 attention prologue, fused: per-head RMSNorm over head_dim on q
+    and k, RoPE in place, rotated k and v scattered into the paged cache
+    (one launch per layer). Head dims outside the fused kernel's set compose
+    the rmsnorm and rope_and_cache kernels instead (three launches, and one
+    extra rounding to the storage dtype between norm and rotation)."""
+    if _use_hip(q):
+        D = q.shape[-1]
+        if D in _QKNORM_HEAD_DIMS:
+            _EXT.qknorm_rope_and_cache(
+                q, k, v, k_cache, v_cache, q_weight, k_weight, eps, offset,
+                positions, cos_sin, slot_mapping)
+            return
+        for t, w in ((q, q_weight), (k, k_weight)):
+            t.copy_(rmsnorm(t.reshape(-1, D), w, eps, offset).view(t.shape))
+        rope_and_cache(q, k, v, k_cache, v_cache, positions, cos_sin, slot_mapping)
+        return
+    torch_ref.qknorm_rope_and_cache(
+        q, k, v, k_cache, v_cache, q_weight, k_weight, eps, offset,
+        positions, cos_sin, slot_mapping)
+
+
 # ------------------------------------------------------------- KV cache --
 
 

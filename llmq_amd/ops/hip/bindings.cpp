@@ -225,6 +225,84 @@ void rope_and_cache(at::Tensor q, at::Tensor k, at::Tensor value,
   });
 }
 
+// Qwen3: per-head RMSNorm on q and k fused in front of rope_and_cache.
+void qknorm_rope_and_cache(at::Tensor q, at::Tensor k, at::Tensor value,
+                           at::Tensor k_cache, at::Tensor v_cache,
+                           at::Tensor q_weight, at::Tensor k_weight,
+                           double eps, double offset, at::Tensor positions,
+                           at::Tensor cos_sin, at::Tensor slot_mapping) {
+  CHECK_GPU(q);
+  CHECK_LASTDIM(q);
+  CHECK_LASTDIM(k);
+  CHECK_LASTDIM(value);
+  TORCH_CHECK(q.dim() == 3 && k.dim() == 3 && value.dim() == 3,
+              "q/k/v must be [T, H, D]");
+  TORCH_CHECK(cos_sin.scalar_type() == at::kFloat);
+  TORCH_CHECK(slot_mapping.scalar_type() == at::kLong);
+  TORCH_CHECK(positions.scalar_type() == at::kLong);
+  const int T_ = q.size(0);
+  if (T_ == 0) return;
+  const int hq = q.size(1), hk = k.size(1), d = q.size(2);
+  const int bs = k_cache.size(2);
+  TORCH_CHECK(d == 64 || d == 128 || d == 256,
+              "qknorm_rope_and_cache: head_dim must be 64, 128 or 256, got ", d);
+  TORCH_CHECK(k.size(0) == T_ && value.size(0) == T_ &&
+              positions.numel() == T_ && slot_mapping.numel() == T_,
+              "k/v/positions/slot_mapping must have one row per token");
+  TORCH_CHECK(k.size(2) == d && value.size(2) == d && value.size(1) == hk,
+              "k/v head shape mismatch");
+  TORCH_CHECK(k.scalar_type() == q.scalar_type() &&
+              value.scalar_type() == q.scalar_type(), "q/k/v dtype mismatch");
+  TORCH_CHECK(q.stride(1) == d && k.stride(1) == d && value.stride(1) == d,
+              "head dim must be packed");
+  TORCH_CHECK(k_cache.is_contiguous() && v_cache.is_contiguous());
+  TORCH_CHECK(k_cache.size(1) == hk && k_cache.size(3) == d &&
+              v_cache.sizes() == k_cache.sizes(), "cache shape mismatch");
+  TORCH_CHECK(cos_sin.is_contiguous() && cos_sin.size(-1) == d,
+              "cos_sin must be contiguous [max_pos, head_dim]");
+  for (const at::Tensor* w : {&q_weight, &k_weight}) {
+    TORCH_CHECK(w->is_cuda() && w->is_contiguous() && w->numel() == d &&
+                w->scalar_type() == q.scalar_type(),
+                "q/k norm weights must be contiguous [head_dim] of q's dtype");
+  }
+  // A lane moves D/32 elements per half in pieces of at most 16 bytes; every
+  // address it forms is base + row*stride + a multiple of that piece.
+  const long esz = q.element_size();
+  const long piece = std::min<long>(16, (d / 32) * esz);
+  auto aligned = [&](const at::Tensor& t, long row_stride, long align) {
+    return reinterpret_cast<uintptr_t>(t.data_ptr()) % align == 0 &&
+           (row_stride * t.element_size()) % align == 0;
+  };
+  TORCH_CHECK(aligned(q, q.stride(0), piece) && aligned(k, k.stride(0), piece) &&
+              aligned(q_weight, 0, piece) && aligned(k_weight, 0, piece),
+              "q/k/weights must be aligned to ", piece, " bytes");
+  TORCH_CHECK(aligned(value, value.stride(0), 16) && aligned(k_cache, 0, 16) &&
+              aligned(v_cache, 0, 16) && aligned(cos_sin, 0, 16),
+              "value/caches/cos_sin must be 16-byte aligned");
+  const bool fp8_cache = k_cache.scalar_type() == at::kFloat8_e4m3fn;
+  TORCH_CHECK(fp8_cache || k_cache.scalar_type() == q.scalar_type(),
+              "cache dtype must be q's dtype or float8_e4m3fn");
+  TORCH_CHECK(v_cache.scalar_type() == k_cache.scalar_type());
+  dispatch_dtype(q, "qknorm_rope_and_cache", [&]<typename T>() {
+    dispatch_cache_type<T>(fp8_cache, [&]<typename TC>() {
+      dispatch_head_dim<64, 128, 256>(d, [&]<int HD>() {
+        hipLaunchKernelGGL(
+            (qknorm_rope_and_cache_kernel<T, TC, HD>), dim3(T_), dim3(256), 0,
+            stream(), reinterpret_cast<T*>(q.data_ptr()),
+            reinterpret_cast<T*>(k.data_ptr()),
+            reinterpret_cast<const T*>(value.data_ptr()),
+            reinterpret_cast<TC*>(k_cache.data_ptr()),
+            reinterpret_cast<TC*>(v_cache.data_ptr()),
+            reinterpret_cast<const T*>(q_weight.data_ptr()),
+            reinterpret_cast<const T*>(k_weight.data_ptr()), (float)eps,
+            (float)offset, positions.data_ptr<long>(),
+            cos_sin.data_ptr<float>(), slot_mapping.data_ptr<long>(), hq, hk,
+            bs, q.stride(0), k.stride(0), value.stride(0));
+      });
+    });
+  });
+}
+
 // ------------------------------------------------------------ attention --
 
 template <typename T>
@@ -572,6 +650,7 @@ TORCH_LIBRARY(llmq_amd, m) {
   m.def("skinny_gemm(Tensor(a!) out, Tensor x, Tensor w, Tensor? bias, int splitk) -> ()");
   m.def("norm_add_norm(Tensor(a!) x, Tensor(b!) residual, Tensor w_post, Tensor w_pre, float eps, float offset) -> ()");
   m.def("rope_and_cache(Tensor(a!) q, Tensor(b!) k, Tensor value, Tensor(c!) k_cache, Tensor(d!) v_cache, Tensor positions, Tensor cos_sin, Tensor slot_mapping) -> ()");
+  m.def("qknorm_rope_and_cache(Tensor(a!) q, Tensor(b!) k, Tensor value, Tensor(c!) k_cache, Tensor(d!) v_cache, Tensor q_weight, Tensor k_weight, float eps, float offset, Tensor positions, Tensor cos_sin, Tensor slot_mapping) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(llmq_amd, CUDA, m) {
@@ -588,4 +667,5 @@ TORCH_LIBRARY_IMPL(llmq_amd, CUDA, m) {
   m.impl("skinny_gemm", &skinny_gemm);
   m.impl("norm_add_norm", &norm_add_norm);
   m.impl("rope_and_cache", &rope_and_cache);
+  m.impl("qknorm_rope_and_cache", &qknorm_rope_and_cache);
 }

@@ -117,3 +117,155 @@ __global__ void rope_and_cache_kernel(
     }
   }
 }
+
+// ---- fused QK-norm + RoPE + cache write (Qwen3) ----------------------------
+// Qwen3 applies a per-head RMSNorm over head_dim to q and k between the QKV
+// projection and RoPE. This kernel does that norm where rope_and_cache_kernel
+// already touches every q/k element, so the layer keeps ONE launch here
+// instead of rmsnorm(q) + rmsnorm(k) + rope_and_cache and a second pass over
+// q and k.
+//
+// Mapping: a 16-lane group owns one head (a wave covers 4 heads, the 256-
+// thread block 16 heads per pass). Lane l of the group holds E = D/32
+// contiguous elements of the low half at [l*E, l*E+E) and the matching E
+// elements of the high half at D/2 + [l*E, l*E+E), so a rotate-half partner
+// pair (d, d + D/2) is lane-local and the only cross-lane traffic is the
+// sum of squares: four __shfl_xor steps that never leave the group. No LDS,
+// no __syncthreads. Groups of one wave may run different trip counts of the
+// head loop; a group is wholly active or wholly inactive, and xor offsets
+// below 16 stay inside it, so an active lane never reads an inactive one.
+//
+// Each half is moved in pieces of min(16, E*sizeof(T)) bytes: 4/8/16 bytes
+// for 2-byte T at D = 64/128/256 and 8/16/2x16 bytes for fp32.
+//
+// Rounding: the normed value stays fp32 into the rotation; the only rounding
+// to T is at the store. An fp8 cache gets the quantization of that T-rounded
+// k, exactly as rope_and_cache_kernel writes it.
+
+template <int BYTES> struct RawBytes;
+template <> struct RawBytes<2> { using type = unsigned short; };
+template <> struct RawBytes<4> { using type = unsigned int; };
+template <> struct RawBytes<8> { using type = uint2; };
+template <> struct RawBytes<16> { using type = uint4; };
+
+// N elements of T in registers, loaded/stored in pieces of at most 16 bytes.
+// The address must be aligned to kPiece.
+template <typename T, int N>
+struct Frag {
+  static constexpr int kBytes = N * (int)sizeof(T);
+  static constexpr int kPiece = kBytes < 16 ? kBytes : 16;
+  static constexpr int kPieces = kBytes / kPiece;
+  using Raw = typename RawBytes<kPiece>::type;
+  alignas(kPiece) T data[N];
+
+  DEVINL void load(const T* p) {
+#pragma unroll
+    for (int i = 0; i < kPieces; ++i)
+      reinterpret_cast<Raw*>(data)[i] = reinterpret_cast<const Raw*>(p)[i];
+  }
+  DEVINL void store(T* p) const {
+#pragma unroll
+    for (int i = 0; i < kPieces; ++i)
+      reinterpret_cast<Raw*>(p)[i] = reinterpret_cast<const Raw*>(data)[i];
+  }
+};
+
+template <typename T, typename TC, int D>
+__global__ __launch_bounds__(256) void qknorm_rope_and_cache_kernel(
+    T* __restrict__ q,             // [T, Hq, D] (row stride q_stride)
+    T* __restrict__ k,             // [T, Hk, D]
+    const T* __restrict__ value,   // [T, Hk, D]
+    TC* __restrict__ k_cache,      // [blocks, Hk, bs, D]
+    TC* __restrict__ v_cache,
+    const T* __restrict__ q_weight,  // [D]
+    const T* __restrict__ k_weight,  // [D]
+    float eps, float offset,
+    const long* __restrict__ positions,
+    const float* __restrict__ cos_sin,  // [max_pos, D] f32
+    const long* __restrict__ slots,
+    int num_q_heads, int num_k_heads, int block_size,
+    long q_stride, long k_stride, long v_stride) {
+  constexpr int GROUP = 16;        // lanes per head
+  constexpr int HALF = D / 2;
+  constexpr int E = D / 32;        // elements per lane per half
+  const int token = blockIdx.x;
+  const long pos = positions[token];
+  const long slot = slots[token];
+  const long block = slot / block_size;
+  const int off = (int)(slot % block_size);
+  const int gl = threadIdx.x % GROUP;   // lane within the head's group
+  const int groups = blockDim.x / GROUP;
+  const int d0 = gl * E;                // this lane's offset in each half
+
+  Frag<float, E> c, s;
+  c.load(cos_sin + pos * D + d0);
+  s.load(cos_sin + pos * D + HALF + d0);
+
+  const int heads = num_q_heads + num_k_heads;
+  for (int h = threadIdx.x / GROUP; h < heads; h += groups) {
+    const bool is_q = h < num_q_heads;
+    const int kh = h - num_q_heads;
+    T* base = is_q ? q + (long)token * q_stride + (long)h * D
+                   : k + (long)token * k_stride + (long)kh * D;
+    const T* w = is_q ? q_weight : k_weight;
+    Frag<T, E> lo, hi, wlo, whi;
+    lo.load(base + d0);
+    hi.load(base + HALF + d0);
+    wlo.load(w + d0);
+    whi.load(w + HALF + d0);
+
+    float x1[E], x2[E];
+    float ss = 0.f;
+#pragma unroll
+    for (int j = 0; j < E; ++j) {
+      x1[j] = to_f32(lo.data[j]);
+      x2[j] = to_f32(hi.data[j]);
+      ss += x1[j] * x1[j] + x2[j] * x2[j];
+    }
+    ss = group_reduce_sum<GROUP>(ss);
+    const float inv = rsqrtf(ss / D + eps);
+#pragma unroll
+    for (int j = 0; j < E; ++j) {
+      const float y1 = x1[j] * inv * (to_f32(wlo.data[j]) + offset);
+      const float y2 = x2[j] * inv * (to_f32(whi.data[j]) + offset);
+      lo.data[j] = from_f32<T>(y1 * c.data[j] - y2 * s.data[j]);
+      hi.data[j] = from_f32<T>(y2 * c.data[j] + y1 * s.data[j]);
+    }
+    lo.store(base + d0);
+    hi.store(base + HALF + d0);
+    if (!is_q && slot >= 0) {
+      TC* kdst = k_cache +
+          ((block * num_k_heads + kh) * (long)block_size + off) * D;
+      if constexpr (std::is_same_v<T, TC>) {
+        lo.store(kdst + d0);
+        hi.store(kdst + HALF + d0);
+      } else {  // quantize the T-rounded rotated k
+        Frag<TC, E> clo, chi;
+#pragma unroll
+        for (int j = 0; j < E; ++j) {
+          clo.data[j] = from_f32<TC>(to_f32(lo.data[j]));
+          chi.data[j] = from_f32<TC>(to_f32(hi.data[j]));
+        }
+        clo.store(kdst + d0);
+        chi.store(kdst + HALF + d0);
+      }
+    }
+  }
+  if (slot < 0) return;
+  // copy v (vectorized; untouched by norm and rope)
+  constexpr int VE = Vec8<T>::kElems;
+  const int vchunks = (num_k_heads * D) / VE;
+  for (int i = threadIdx.x; i < vchunks; i += blockDim.x) {
+    const int h = (i * VE) / D;
+    const int d = (i * VE) % D;
+    Vec8<T> vv = load16(value + (long)token * v_stride + (long)h * D + d);
+    TC* vdst = v_cache +
+        ((block * num_k_heads + h) * (long)block_size + off) * D + d;
+    if constexpr (std::is_same_v<T, TC>) {
+      store16(vdst, vv);
+    } else {
+#pragma unroll
+      for (int j = 0; j < VE; ++j) vdst[j] = from_f32<TC>(to_f32(vv.data[j]));
+    }
+  }
+}

@@ -127,6 +127,42 @@ def reshape_and_cache(
     v_cache[blocks, :, offs, :] = value.to(v_cache.dtype)
 
 
+def qknorm_rope_and_cache(
+    q: torch.Tensor,  # [T, num_heads, head_dim]
+    k: torch.Tensor,  # [T, num_kv_heads, head_dim]
+    v: torch.Tensor,
+    k_cache: torch.Tensor,
+    v_cache: torch.Tensor,
+    q_weight: torch.Tensor,  # [head_dim]
+    k_weight: torch.Tensor,
+    eps: float,
+    offset: float,
+    positions: torch.Tensor,
+    cos_sin: torch.Tensor,
+    slot_mapping: torch.Tensor,
+) -> None:
+    """Qwen3 attention prologue: per-head RMSNorm over head_dim on q and k,
+    NeoX RoPE, then the paged-cache write. Mirrors the fused kernel's
+    rounding: the normed values stay fp32 into the rotation and are cast to
+    q.dtype ONCE (rmsnorm + rope_inplace would round in between). Rows with
+    a negative slot (graph padding) are normed and rotated but not cached."""
+    half = q.shape[-1] // 2
+    cs = cos_sin[positions].float()
+    cos = cs[:, :half].unsqueeze(1)
+    sin = cs[:, half:].unsqueeze(1)
+    for t, w in ((q, q_weight), (k, k_weight)):
+        xf = t.float()
+        var = xf.pow(2).mean(dim=-1, keepdim=True)
+        xf = xf * torch.rsqrt(var + eps) * (w.float() + offset)
+        x1, x2 = xf[..., :half], xf[..., half:]
+        t.copy_(torch.cat([x1 * cos - x2 * sin, x2 * cos + x1 * sin], dim=-1))
+    keep = slot_mapping >= 0
+    if bool(keep.all()):
+        reshape_and_cache(k, v, k_cache, v_cache, slot_mapping)
+    else:
+        reshape_and_cache(k[keep], v[keep], k_cache, v_cache, slot_mapping[keep])
+
+
 def _softcap(scores: torch.Tensor, cap: float) -> torch.Tensor:
     if cap and cap > 0:
         return torch.tanh(scores / cap) * cap

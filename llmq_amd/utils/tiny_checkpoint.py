@@ -1,7 +1,7 @@
 """Build a tiny REAL-layout checkpoint offline (testing utility).
 
 Produces what a HuggingFace hub download would: config.json +
-model.safetensors (Llama/Qwen2/Gemma-2 layout) + a real ``tokenizer.json``
+model.safetensors (Llama/Qwen2/Qwen3/Gemma-2 layout) + a real ``tokenizer.json``
 (WordLevel, built with the `tokenizers` library) + tokenizer_config.json
 with a chat template. Lets GPU boxes (no network) exercise the FULL
 serving path the reference gets from real checkpoints: load from disk →
@@ -57,6 +57,21 @@ def build_tiny_checkpoint(
             bos_token_id=1, eos_token_id=2,
         )
         model = transformers.Qwen2ForCausalLM(cfg)
+    elif family == "qwen3":
+        cfg = transformers.Qwen3Config(
+            vocab_size=vocab_size, hidden_size=hidden, intermediate_size=hidden * 2,
+            num_hidden_layers=layers, num_attention_heads=heads,
+            num_key_value_heads=kv_heads, head_dim=hidden // heads,
+            max_position_embeddings=2048, rope_theta=10000.0, rms_norm_eps=1e-6,
+            tie_word_embeddings=False, bos_token_id=1, eos_token_id=2,
+        )
+        model = transformers.Qwen3ForCausalLM(cfg)
+        # HF initialises q_norm/k_norm to ones; perturb them so a dropped or
+        # swapped norm weight changes the output.
+        with torch.no_grad():
+            for name, prm in model.named_parameters():
+                if name.endswith(("q_norm.weight", "k_norm.weight")):
+                    prm.copy_(1.0 + 0.25 * torch.randn_like(prm))
     elif family == "gemma2":
         cfg = transformers.Gemma2Config(
             vocab_size=vocab_size, hidden_size=hidden, intermediate_size=hidden * 2,
