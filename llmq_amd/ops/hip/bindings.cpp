@@ -479,11 +479,44 @@ void varlen_prefill_attention(at::Tensor out, at::Tensor q, at::Tensor k,
                               at::Tensor cu_seqlens_k,
                               long max_seqlen, double scale, double softcap,
                               long window) {
-  CHECK_GPU(q);
-  CHECK_LASTDIM(q);
-  TORCH_CHECK(cu_seqlens.scalar_type() == at::kInt);
-  TORCH_CHECK(cu_seqlens_k.scalar_type() == at::kInt);
+  // The kernels address row*stride(0) + head*D + d and stage K/V (bf16: Q
+  // too) with 16-byte loads; anything else would be reinterpreted silently.
+  auto check_operand = [&](const at::Tensor& t, const char* name) {
+    TORCH_CHECK(t.is_cuda(), name, " must be on GPU");
+    TORCH_CHECK(t.dim() == 3, name, " must be [tokens, heads, head_dim]");
+    TORCH_CHECK(t.scalar_type() == q.scalar_type(), name,
+                " must have q's dtype");
+    TORCH_CHECK(t.size(2) == q.size(2), name, " must have q's head_dim");
+    TORCH_CHECK(t.stride(2) == 1 && t.stride(1) == t.size(2), name,
+                " must have unit last-dim stride and head stride == head_dim");
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0 &&
+                    t.stride(0) * t.element_size() % 16 == 0,
+                name, " must be 16-byte aligned with a row stride that is a "
+                "multiple of 16 bytes");
+  };
+  TORCH_CHECK(q.dim() == 3, "q must be [tokens, heads, head_dim]");
+  check_operand(q, "q");
+  check_operand(k, "k");
+  check_operand(v, "v");
+  check_operand(out, "out");
+  TORCH_CHECK(out.sizes() == q.sizes(), "out must have q's shape");
+  TORCH_CHECK(v.sizes() == k.sizes(), "v must have k's shape");
+  TORCH_CHECK(k.size(1) > 0 && q.size(1) % k.size(1) == 0,
+              "num_heads must be a multiple of num_kv_heads");
+  auto check_offsets = [&](const at::Tensor& t, const char* name) {
+    TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kInt && t.dim() == 1 &&
+                    t.is_contiguous(),
+                name, " must be a contiguous 1-D int32 GPU tensor");
+  };
+  check_offsets(cu_seqlens, "cu_seqlens");
+  check_offsets(cu_seqlens_k, "cu_seqlens_k");
+  TORCH_CHECK(cu_seqlens.size(0) >= 1 &&
+                  cu_seqlens.size(0) == cu_seqlens_k.size(0),
+              "cu_seqlens and cu_seqlens_k must have equal length >= 1");
+  TORCH_CHECK(window >= 0 && max_seqlen >= 0,
+              "window and max_seqlen must be >= 0");
   const int B = cu_seqlens.size(0) - 1;
+  if (B == 0 || q.size(0) == 0) return;
   dispatch_dtype(q, "varlen_prefill_attention", [&]<typename T>() {
     launch_prefill<T>(out, q, k, v, cu_seqlens, cu_seqlens_k, B, scale,
                       softcap, window, max_seqlen);
