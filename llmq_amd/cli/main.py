@@ -238,6 +238,8 @@ def worker() -> None:
 @click.option("--prefetch", type=int, default=None)
 @click.option("--kv-cache-dtype", type=click.Choice(["auto", "fp8"]), default="auto",
               help="KV storage dtype; fp8 (OCP e4m3) doubles KV capacity")
+@click.option("--enable-prefix-caching", is_flag=True, default=False,
+              help="Reuse the KV of shared prompt heads across jobs")
 @click.option("--engine-overrides", default=None,
               help='JSON dict of EngineConfig overrides, e.g. \'{"enforce_eager": true}\'')
 @click.option("--data-parallel-size", "-dp", type=int, default=None,
@@ -245,7 +247,8 @@ def worker() -> None:
                    "(reference main.py:433-439 passes this to vLLM; here it "
                    "spawns N workers competing on the same queue)")
 def worker_run(model, queue_name, tensor_parallel_size, max_num_seqs, max_model_len,
-               prefetch, kv_cache_dtype, engine_overrides, data_parallel_size):
+               prefetch, kv_cache_dtype, enable_prefix_caching, engine_overrides,
+               data_parallel_size):
     """GPU inference worker (in-tree MI355X engine)."""
     import json as _json
 
@@ -254,6 +257,8 @@ def worker_run(model, queue_name, tensor_parallel_size, max_num_seqs, max_model_
     overrides = _json.loads(engine_overrides) if engine_overrides else {}
     if kv_cache_dtype != "auto":
         overrides.setdefault("kv_cache_dtype", kv_cache_dtype)
+    if enable_prefix_caching:
+        overrides.setdefault("enable_prefix_caching", True)
     if data_parallel_size and data_parallel_size > 1:
         run_engine_worker_dp(
             model, queue_name, data_parallel_size,

@@ -140,6 +140,10 @@ class Config(BaseModel):
         default_factory=lambda: _env_bool("LLMQ_HIPGRAPH", True),
         description="Capture the decode step as a hipGraph",
     )
+    enable_prefix_caching: bool = Field(
+        default_factory=lambda: _env_bool("LLMQ_PREFIX_CACHING", False),
+        description="Reuse the KV of shared prompt heads across jobs",
+    )
     temperature: float = Field(
         default_factory=lambda: _env_float("LLMQ_TEMPERATURE", 0.7),
         description="Default sampling temperature (reference hardcodes 0.7)",

@@ -92,6 +92,7 @@ class Result(BaseModel):
     prefill_ms: Optional[float] = Field(None)
     decode_ms: Optional[float] = Field(None)
     prompt_tokens: Optional[int] = Field(None)
+    cached_tokens: Optional[int] = Field(None, description="Prompt tokens served from the prefix cache")
     output_tokens: Optional[int] = Field(None)
     finish_reason: Optional[str] = Field(None, description="stop | length | eos")
 

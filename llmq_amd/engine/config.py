@@ -30,6 +30,9 @@ class EngineConfig:
     # CPU-test override: number of KV blocks (None → sized from free HBM)
     num_kv_blocks: Optional[int] = None
     enforce_eager: bool = False
+    # Automatic prefix caching: full KV blocks of finished/running prompts
+    # are kept and shared with later prompts that start with the same tokens.
+    enable_prefix_caching: bool = False
 
     def resolve_device(self) -> torch.device:
         if self.device == "auto":

@@ -23,7 +23,7 @@ import torch
 
 from llmq_amd import ops
 from llmq_amd.engine.config import EngineConfig
-from llmq_amd.engine.kv_cache import BlockAllocator, KVCache
+from llmq_amd.engine.kv_cache import BlockAllocator, KVCache, PrefixCachingAllocator
 from llmq_amd.engine.model_runner import ModelRunner
 from llmq_amd.engine.model_specs import ModelSpec, resolve_spec
 from llmq_amd.engine.models.llama import CausalLM
@@ -83,6 +83,7 @@ class RequestOutput:
     text: str = ""
     prompt_tokens: int = 0
     output_tokens: int = 0
+    cached_tokens: int = 0  # prompt tokens served from the prefix cache
     queue_wait_ms: Optional[float] = None
     prefill_ms: Optional[float] = None
     decode_ms: Optional[float] = None
@@ -139,7 +140,10 @@ class LLMEngine:
             self.spec.num_layers, num_blocks, kv_heads_local,
             config.kv_block_size, self.spec.head_dim, self.device, self.kv_dtype,
         )
-        self.allocator = BlockAllocator(num_blocks)
+        self.allocator = (
+            PrefixCachingAllocator(num_blocks, config.kv_block_size)
+            if config.enable_prefix_caching else BlockAllocator(num_blocks)
+        )
         self.scheduler = Scheduler(
             self.allocator,
             config.kv_block_size,
@@ -286,6 +290,15 @@ class LLMEngine:
         self._seqs.pop(request_id, None)
         self._prefill_done_at.pop(request_id, None)
 
+    def prefix_cache_stats(self) -> Dict[str, int]:
+        """Prefix-cache counters: prompt tokens looked up and hit at
+        admission, blocks currently cached, blocks evicted. All zero when
+        enable_prefix_caching is off."""
+        if isinstance(self.allocator, PrefixCachingAllocator):
+            return self.allocator.stats()
+        return {"lookup_tokens": 0, "hit_tokens": 0, "cached_blocks": 0,
+                "evictions": 0}
+
     def has_unfinished(self) -> bool:
         return self.scheduler.has_work()
 
@@ -357,7 +370,7 @@ class LLMEngine:
             chunks = batch.chunks or [(0, sq.num_tokens) for sq in pseqs]
             final = []
             for sq, (st, e) in zip(pseqs, chunks):
-                if st == 0:
+                if sq.prefill_start_time is None:  # first scheduled chunk
                     sq.prefill_start_time = now
                 sq.prefilled = e
                 if e == sq.num_tokens:
@@ -379,6 +392,7 @@ class LLMEngine:
                 new_token_ids=[tok],
                 prompt_tokens=seq.prompt_len,
                 output_tokens=nt - seq.prompt_len,
+                cached_tokens=seq.cached_tokens,
             )
             # Cheap pre-check: most decode steps finish nothing; only take
             # the full _check_finish path (stop-string decode etc.) when a

@@ -7,17 +7,28 @@ import torch
 
 
 @dataclass
-class ChunkGather:
-    """Chunked-prefill context assembly: per layer, the attention K/V is the
-    GATHERED past (from the paged cache) interleaved with the fresh chunk
-    rows. Indices are precomputed once per step."""
+class TorchGatherIndices:
+    """Per-token index tensors of the torch gather composition
+    (LLMQ_PAGED_GATHER=0, A/B and bisection only)."""
 
-    cu_seqlens_k: torch.Tensor   # [B+1] int32 key offsets (>= query lens)
     blocks: torch.Tensor         # [P] int64 cache block index per past row
     offs: torch.Tensor           # [P] int64 in-block offset per past row
     past_dst: torch.Tensor       # [P] int64 destination rows in the packed K
     fresh_dst: torch.Tensor      # [Tq] int64 destination rows in the packed K
+
+
+@dataclass
+class ChunkGather:
+    """Context assembly for sequences whose first tokens are already in the
+    paged cache (chunk continuations, prefix-cache hits): per layer, the
+    attention K/V is each sequence's past rows gathered through its block
+    table, followed by its fresh rows. Built once per step, O(blocks)."""
+
+    cu_seqlens_k: torch.Tensor   # [B+1] int32 key offsets (>= query lens)
+    block_tables: torch.Tensor   # [B, W] int32, W >= ceil(max past / block_size)
     total_k: int                 # packed K rows
+    max_seqlen_k: int            # longest context in the segment
+    torch_indices: "TorchGatherIndices | None" = None  # LLMQ_PAGED_GATHER=0
 
 
 @dataclass

@@ -20,8 +20,10 @@ import torch
 
 from llmq_amd import ops
 from llmq_amd.engine.config import EngineConfig
-from llmq_amd.engine.forward_meta import ChunkGather, DecodeMeta, MixedMeta, PrefillMeta
-from llmq_amd.engine.kv_cache import KVCache
+from llmq_amd.engine.forward_meta import (
+    ChunkGather, DecodeMeta, MixedMeta, PrefillMeta, TorchGatherIndices,
+)
+from llmq_amd.engine.kv_cache import KVCache, blocks_needed
 from llmq_amd.engine.models.llama import CausalLM
 from llmq_amd.engine.scheduler import ScheduledBatch, Sequence
 
@@ -72,6 +74,12 @@ class ModelRunner:
         # for comparison; both sample identical tokens.
         self.fused_logit_tail = device.type == "cuda" and os.environ.get(
             "LLMQ_FUSED_LOGIT_TAIL", "1") not in ("0", "false", "")
+        # Chunk continuations and prefix-cache hits assemble their attention
+        # context with the gather_paged_kv kernel. LLMQ_PAGED_GATHER=0 keeps
+        # the torch composition it replaced (advanced-index reads + casts +
+        # index_copy_, per-token index lists) for A/B and bisection.
+        self.paged_gather = os.environ.get(
+            "LLMQ_PAGED_GATHER", "1") not in ("0", "false", "")
         if self.use_graphs:
             self._alloc_static_buffers()
 
@@ -159,11 +167,6 @@ class ModelRunner:
         cu_k = [0]
         rel_last: List[int] = []
         any_chunk = any(start > 0 for (start, _e) in chunks)
-        g_blocks: List[int] = []
-        g_offs: List[int] = []
-        past_dst: List[int] = []
-        fresh_dst: List[int] = []
-        krow = 0
         for seq, (start, end) in zip(pseqs, chunks):
             n = end - start
             ids.extend(seq.token_ids[start:end])
@@ -173,27 +176,28 @@ class ModelRunner:
             if end == seq.num_tokens:
                 rel_last.append(cu[-1] + n - 1)
             cu.append(cu[-1] + n)
-            if any_chunk:
-                for p in range(start):  # past rows gathered from the cache
-                    g_blocks.append(bt[p // bs])
-                    g_offs.append(p % bs)
-                    past_dst.append(krow)
-                    krow += 1
-                for i in range(cu[-2], cu[-1]):
-                    fresh_dst.append(krow)
-                    krow += 1
             cu_k.append(cu_k[-1] + end)  # keys = full context so far
         slot_mapping = torch.tensor(slots, dtype=torch.long, device=dev)
         gather = None
         if any_chunk:
+            # One padded block-table row per sequence covering its past rows
+            # [0, start): O(blocks) host work. Pad entries are never read
+            # (rows past a sequence's own past come from the fresh chunk);
+            # block 0 keeps them valid ids all the same.
+            width = max(1, max(blocks_needed(st, bs) for (st, _e) in chunks))
+            bt_np = np.zeros((len(pseqs), width), dtype=np.int32)
+            for i, (seq, (start, _e)) in enumerate(zip(pseqs, chunks)):
+                nb = blocks_needed(start, bs)
+                bt_np[i, :nb] = seq.block_table[:nb]
             gather = ChunkGather(
                 cu_seqlens_k=torch.tensor(cu_k, dtype=torch.int32, device=dev),
-                blocks=torch.tensor(g_blocks, dtype=torch.long, device=dev),
-                offs=torch.tensor(g_offs, dtype=torch.long, device=dev),
-                past_dst=torch.tensor(past_dst, dtype=torch.long, device=dev),
-                fresh_dst=torch.tensor(fresh_dst, dtype=torch.long, device=dev),
-                total_k=krow,
+                block_tables=torch.from_numpy(bt_np).to(dev),
+                total_k=cu_k[-1],
+                max_seqlen_k=max(e for (_st, e) in chunks),
             )
+            if not self.paged_gather:
+                gather.torch_indices = self._torch_gather_indices(
+                    pseqs, chunks, dev)
         meta = PrefillMeta(
             cu_seqlens=torch.tensor(cu, dtype=torch.int32, device=dev),
             max_seqlen=max(e - st for (st, e) in chunks),
@@ -201,6 +205,31 @@ class ModelRunner:
             gather=gather,
         )
         return ids, pos, slot_mapping, meta, rel_last
+
+    def _torch_gather_indices(self, pseqs, chunks, dev) -> TorchGatherIndices:
+        """Per-token indices of the torch gather composition
+        (LLMQ_PAGED_GATHER=0 only: O(tokens) host work)."""
+        bs = self.block_size
+        g_blocks: List[int] = []
+        g_offs: List[int] = []
+        past_dst: List[int] = []
+        fresh_dst: List[int] = []
+        krow = 0
+        for seq, (start, end) in zip(pseqs, chunks):
+            bt = seq.block_table
+            for p in range(start):  # past rows gathered from the cache
+                g_blocks.append(bt[p // bs])
+                g_offs.append(p % bs)
+                past_dst.append(krow)
+                krow += 1
+            fresh_dst.extend(range(krow, krow + end - start))
+            krow += end - start
+        return TorchGatherIndices(
+            blocks=torch.tensor(g_blocks, dtype=torch.long, device=dev),
+            offs=torch.tensor(g_offs, dtype=torch.long, device=dev),
+            past_dst=torch.tensor(past_dst, dtype=torch.long, device=dev),
+            fresh_dst=torch.tensor(fresh_dst, dtype=torch.long, device=dev),
+        )
 
     @torch.no_grad()
     def execute_prefill(self, seqs: List[Sequence], chunks=None, buf_name: str = "main") -> torch.Tensor:

@@ -227,15 +227,22 @@ class CausalLM:
                 q, k, v, pmeta.cu_seqlens, pmeta.max_seqlen, s.scale,
                 s.attn_softcap, window,
             )
-        KVH, D = k.shape[1], k.shape[2]
-        k_att = q.new_empty(g.total_k, KVH, D)
-        v_att = q.new_empty(g.total_k, KVH, D)
-        past_k = kv_cache.k[layer][g.blocks, :, g.offs].to(q.dtype)
-        past_v = kv_cache.v[layer][g.blocks, :, g.offs].to(q.dtype)
-        k_att.index_copy_(0, g.past_dst, past_k)
-        v_att.index_copy_(0, g.past_dst, past_v)
-        k_att.index_copy_(0, g.fresh_dst, k)
-        v_att.index_copy_(0, g.fresh_dst, v)
+        ti = g.torch_indices
+        if ti is None:
+            k_att, v_att = ops.gather_paged_kv(
+                kv_cache.k[layer], kv_cache.v[layer], k, v, g.block_tables,
+                pmeta.cu_seqlens, g.cu_seqlens_k, g.total_k, g.max_seqlen_k,
+            )
+        else:  # LLMQ_PAGED_GATHER=0: the torch composition (A/B, bisection)
+            KVH, D = k.shape[1], k.shape[2]
+            k_att = q.new_empty(g.total_k, KVH, D)
+            v_att = q.new_empty(g.total_k, KVH, D)
+            past_k = kv_cache.k[layer][ti.blocks, :, ti.offs].to(q.dtype)
+            past_v = kv_cache.v[layer][ti.blocks, :, ti.offs].to(q.dtype)
+            k_att.index_copy_(0, ti.past_dst, past_k)
+            v_att.index_copy_(0, ti.past_dst, past_v)
+            k_att.index_copy_(0, ti.fresh_dst, k)
+            v_att.index_copy_(0, ti.fresh_dst, v)
         return ops.varlen_prefill_attention(
             q, k_att, v_att, pmeta.cu_seqlens, pmeta.max_seqlen, s.scale,
             s.attn_softcap, window, cu_seqlens_k=g.cu_seqlens_k,

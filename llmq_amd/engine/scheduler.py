@@ -47,7 +47,7 @@ class Sequence:
         "request_id", "token_ids", "prompt_len", "params", "status",
         "block_table", "arrival_time", "first_token_time", "finish_reason",
         "output_text", "num_preemptions", "prefilled", "prefill_start_time",
-        "uid",
+        "uid", "cached_tokens",
     )
 
     def __init__(self, request_id: str, prompt_token_ids: List[int], params: SamplingParams,
@@ -70,6 +70,7 @@ class Sequence:
         self.num_preemptions = 0
         self.prefilled = 0  # context tokens whose KV is in the cache
         self.prefill_start_time: Optional[float] = None
+        self.cached_tokens = 0  # prefix-cache hit of the latest admission
 
     @property
     def num_tokens(self) -> int:
@@ -116,6 +117,8 @@ class Scheduler:
         self.running: List[Sequence] = []
         # long prompts being prefilled chunk-by-chunk (not yet decodable)
         self.prefilling: List[Sequence] = []
+        # PrefixCachingAllocator: admission looks up the prompt's head first
+        self.prefix_caching = hasattr(allocator, "lookup")
 
     # -- public ----------------------------------------------------------
 
@@ -206,6 +209,7 @@ class Scheduler:
             prefills.append(seq)
             chunks.append((start, end))
             budget -= end - start
+            self._share_chunk(seq, start, end)
         # (b) admit new sequences. Seats are held not just by this step's
         # prefill segment but also by chunked sequences STRANDED this step
         # (budget/allocation ran out above) — they still occupy KV blocks
@@ -219,18 +223,32 @@ class Scheduler:
         ):
             seq = self.waiting[0]
             n = seq.num_tokens
-            end = min(n, budget)
+            # Prefix cache: the hit blocks already hold the KV of [0, hit);
+            # the sequence enters as a chunk continuation at `hit` and only
+            # the fresh tokens are charged to the budget.
+            hit_blocks = (
+                self.allocator.lookup(seq.token_ids) if self.prefix_caching else []
+            )
+            hit = len(hit_blocks) * bs
+            end = min(n, hit + budget)
             if end < n and prefills:
+                self.allocator.free(hit_blocks)
                 break  # start a long prompt's first chunk only at segment head
-            blocks = self.allocator.allocate(blocks_needed(end, bs))
+            blocks = self.allocator.allocate(blocks_needed(end, bs) - len(hit_blocks))
             if blocks is None:
+                self.allocator.free(hit_blocks)  # give the references back
                 break
-            seq.block_table = blocks
+            seq.block_table = hit_blocks + blocks
+            seq.prefilled = hit
+            seq.cached_tokens = hit
             seq.status = SeqStatus.RUNNING
             self.waiting.popleft()
             prefills.append(seq)
-            chunks.append((0, end))
-            budget -= end
+            chunks.append((hit, end))
+            budget -= end - hit
+            if self.prefix_caching:
+                self.allocator.note_admission(n, hit)
+                self._share_chunk(seq, hit, end)
             if end < n:
                 break  # chunked head consumed the budget
         # move bookkeeping: where does each prefill seq live after this step?
@@ -246,6 +264,27 @@ class Scheduler:
         return prefills, chunks
 
     # -- internals -------------------------------------------------------
+
+    def _share_chunk(self, seq: Sequence, start: int, end: int) -> None:
+        """Prefix caching: check chunk [start, end) writes private blocks
+        only, then publish the sequence's full blocks up to `end`."""
+        if not self.prefix_caching:
+            return
+        bs = self.block_size
+        # No copy-on-write: hits are block aligned, so the first fresh token
+        # starts a private block.
+        for b in seq.block_table[start // bs: blocks_needed(end, bs)]:
+            assert self.allocator.refcount(b) == 1, (
+                f"seq {seq.request_id}: write slot in shared block {b}"
+            )
+        # Registered when the chunk is SCHEDULED, not after the step: a
+        # sequence admitted later in this same segment may then hit these
+        # blocks (a queue delivering hundreds of same-template jobs into one
+        # step). That is valid because forward writes every row of the packed
+        # segment into the cache (rope_and_cache / qknorm_rope_and_cache)
+        # before that layer's attention gathers from it, all prefill work
+        # runs on one stream, and step() joins the decode stream at its end.
+        self.allocator.register(seq.token_ids, seq.block_table, end)
 
     def _release(self, seq: Sequence) -> None:
         if seq.block_table:
@@ -267,6 +306,11 @@ class Scheduler:
         while i < len(self.running):
             seq = self.running[i]
             if len(seq.token_ids) <= len(seq.block_table) * bs:
+                if self.prefix_caching:
+                    b = seq.block_table[(len(seq.token_ids) - 1) // bs]
+                    assert self.allocator.refcount(b) == 1, (
+                        f"seq {seq.request_id}: write slot in shared block {b}"
+                    )
                 i += 1
                 continue
             need = blocks_needed(seq.num_tokens, self.block_size) - len(seq.block_table)
@@ -293,6 +337,6 @@ class Scheduler:
         self._release(seq)
         seq.status = SeqStatus.WAITING
         seq.num_preemptions += 1
-        seq.prefilled = 0  # cache gone: the whole context re-prefills
+        seq.prefilled = 0  # blocks released: re-admission re-prefills (or hits)
         self.running.remove(seq)
         self.waiting.appendleft(seq)

@@ -202,6 +202,37 @@ def reshape_and_cache(
     torch_ref.reshape_and_cache(key, value, k_cache, v_cache, slot_mapping)
 
 
+def gather_paged_kv(
+    k_cache: torch.Tensor,       # [num_blocks, kv_heads, block_size, head_dim]
+    v_cache: torch.Tensor,
+    k_fresh: torch.Tensor,       # [Tq, kv_heads, head_dim] (views of the qkv GEMM output)
+    v_fresh: torch.Tensor,
+    block_tables: torch.Tensor,  # [B, W] int32, W >= ceil(max past / block_size)
+    cu_seqlens: torch.Tensor,    # [B+1] int32 fresh-row offsets
+    cu_seqlens_k: torch.Tensor,  # [B+1] int32 context-row offsets
+    total_k: int,
+    max_seqlen_k: int,
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Assemble the packed attention context of a prefill segment whose
+    sequences have part of their context in the paged cache (chunked
+    prefill, prefix-cache hits): per sequence the past rows gathered through
+    its block table, then its fresh rows. One launch per layer. Returns
+    (k_att, v_att), each [total_k, kv_heads, head_dim] in k_fresh's dtype; an
+    fp8 cache is dequantised exactly as `.to(bfloat16)` would."""
+    KVH, D = k_fresh.shape[1], k_fresh.shape[2]
+    k_att = k_fresh.new_empty(total_k, KVH, D)
+    v_att = k_fresh.new_empty(total_k, KVH, D)
+    if _use_hip(k_fresh):
+        _EXT.gather_paged_kv(k_att, v_att, k_cache, v_cache, k_fresh, v_fresh,
+                             block_tables, cu_seqlens, cu_seqlens_k,
+                             int(max_seqlen_k))
+    else:
+        torch_ref.gather_paged_kv(k_att, v_att, k_cache, v_cache, k_fresh,
+                                  v_fresh, block_tables, cu_seqlens,
+                                  cu_seqlens_k, int(max_seqlen_k))
+    return k_att, v_att
+
+
 # ------------------------------------------------------------ attention --
 
 

@@ -303,6 +303,89 @@ void qknorm_rope_and_cache(at::Tensor q, at::Tensor k, at::Tensor value,
   });
 }
 
+// Packed attention context of a prefill segment: gathered past rows from the
+// paged cache followed by this step's fresh rows, per sequence. The caller
+// guarantees what cannot be read here without a device sync: per sequence
+// cu_seqlens_k spans at least cu_seqlens' rows, block_tables is wide enough
+// for the longest past (W >= ceil(max P / bs)) and holds valid block ids,
+// and the offsets stay inside k_out / k_fresh.
+void gather_paged_kv(at::Tensor k_out, at::Tensor v_out, at::Tensor k_cache,
+                     at::Tensor v_cache, at::Tensor k_fresh, at::Tensor v_fresh,
+                     at::Tensor block_tables, at::Tensor cu_seqlens,
+                     at::Tensor cu_seqlens_k, long max_seqlen_k) {
+  TORCH_CHECK(k_cache.is_cuda() && v_cache.is_cuda(), "caches must be on GPU");
+  TORCH_CHECK(k_cache.dim() == 4 && v_cache.sizes() == k_cache.sizes(),
+              "caches must be [blocks, kv_heads, block_size, head_dim]");
+  TORCH_CHECK(k_cache.is_contiguous() && v_cache.is_contiguous(),
+              "caches must be contiguous");
+  TORCH_CHECK(v_cache.scalar_type() == k_cache.scalar_type(),
+              "k_cache/v_cache dtype mismatch");
+  const int kvh = k_cache.size(1), bs = k_cache.size(2), d = k_cache.size(3);
+  const bool fp8_cache = k_cache.scalar_type() == at::kFloat8_e4m3fn;
+  TORCH_CHECK(fp8_cache || k_cache.scalar_type() == k_out.scalar_type(),
+              "cache dtype must be the output dtype or float8_e4m3fn");
+  // Rows move in 16-byte pieces of the cache dtype and of the output dtype.
+  TORCH_CHECK(bs > 0 && d > 0 && (d * k_cache.element_size()) % 16 == 0 &&
+                  (d * k_out.element_size()) % 16 == 0,
+              "head_dim rows must be a multiple of 16 bytes");
+  auto check_rows = [&](const at::Tensor& t, const char* name) {
+    TORCH_CHECK(t.is_cuda(), name, " must be on GPU");
+    TORCH_CHECK(t.dim() == 3 && t.size(1) == kvh && t.size(2) == d, name,
+                " must be [rows, kv_heads, head_dim] of the cache's heads");
+    TORCH_CHECK(t.scalar_type() == k_out.scalar_type(), name,
+                " must have k_out's dtype");
+    TORCH_CHECK(t.stride(2) == 1 && t.stride(1) == d, name,
+                " must have unit last-dim stride and head stride == head_dim");
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0 &&
+                    t.stride(0) * t.element_size() % 16 == 0,
+                name, " must be 16-byte aligned with a row stride that is a "
+                "multiple of 16 bytes");
+  };
+  check_rows(k_out, "k_out");
+  check_rows(v_out, "v_out");
+  check_rows(k_fresh, "k_fresh");
+  check_rows(v_fresh, "v_fresh");
+  TORCH_CHECK(v_out.size(0) == k_out.size(0) && v_fresh.size(0) == k_fresh.size(0),
+              "k/v row counts must match");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(k_cache.data_ptr()) % 16 == 0 &&
+                  reinterpret_cast<uintptr_t>(v_cache.data_ptr()) % 16 == 0,
+              "caches must be 16-byte aligned");
+  auto check_offsets = [&](const at::Tensor& t, const char* name) {
+    TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kInt && t.dim() == 1 &&
+                    t.is_contiguous(),
+                name, " must be a contiguous 1-D int32 GPU tensor");
+  };
+  check_offsets(cu_seqlens, "cu_seqlens");
+  check_offsets(cu_seqlens_k, "cu_seqlens_k");
+  TORCH_CHECK(cu_seqlens.size(0) >= 1 &&
+                  cu_seqlens.size(0) == cu_seqlens_k.size(0),
+              "cu_seqlens and cu_seqlens_k must have equal length >= 1");
+  const int B = cu_seqlens.size(0) - 1;
+  TORCH_CHECK(block_tables.is_cuda() && block_tables.scalar_type() == at::kInt &&
+                  block_tables.dim() == 2 && block_tables.size(0) == B &&
+                  (block_tables.size(1) <= 1 || block_tables.stride(1) == 1),
+              "block_tables must be a [B, W] int32 GPU tensor with contiguous rows");
+  TORCH_CHECK(max_seqlen_k >= 0, "max_seqlen_k must be >= 0");
+  if (B == 0 || max_seqlen_k == 0) return;
+  dim3 grid((unsigned)((max_seqlen_k + GATHER_ROWS - 1) / GATHER_ROWS), B);
+  dispatch_dtype(k_out, "gather_paged_kv", [&]<typename T>() {
+    dispatch_cache_type<T>(fp8_cache, [&]<typename TC>() {
+      hipLaunchKernelGGL(
+          (gather_paged_kv_kernel<T, TC>), grid, dim3(GATHER_THREADS), 0,
+          stream(), reinterpret_cast<T*>(k_out.data_ptr()),
+          reinterpret_cast<T*>(v_out.data_ptr()),
+          reinterpret_cast<const TC*>(k_cache.data_ptr()),
+          reinterpret_cast<const TC*>(v_cache.data_ptr()),
+          reinterpret_cast<const T*>(k_fresh.data_ptr()),
+          reinterpret_cast<const T*>(v_fresh.data_ptr()),
+          block_tables.data_ptr<int>(), cu_seqlens.data_ptr<int>(),
+          cu_seqlens_k.data_ptr<int>(), kvh, d, bs, block_tables.stride(0),
+          k_out.stride(0), v_out.stride(0), k_fresh.stride(0),
+          v_fresh.stride(0));
+    });
+  });
+}
+
 // ------------------------------------------------------------ attention --
 
 template <typename T>
@@ -684,6 +767,7 @@ TORCH_LIBRARY(llmq_amd, m) {
   m.def("norm_add_norm(Tensor(a!) x, Tensor(b!) residual, Tensor w_post, Tensor w_pre, float eps, float offset) -> ()");
   m.def("rope_and_cache(Tensor(a!) q, Tensor(b!) k, Tensor value, Tensor(c!) k_cache, Tensor(d!) v_cache, Tensor positions, Tensor cos_sin, Tensor slot_mapping) -> ()");
   m.def("qknorm_rope_and_cache(Tensor(a!) q, Tensor(b!) k, Tensor value, Tensor(c!) k_cache, Tensor(d!) v_cache, Tensor q_weight, Tensor k_weight, float eps, float offset, Tensor positions, Tensor cos_sin, Tensor slot_mapping) -> ()");
+  m.def("gather_paged_kv(Tensor(a!) k_out, Tensor(b!) v_out, Tensor k_cache, Tensor v_cache, Tensor k_fresh, Tensor v_fresh, Tensor block_tables, Tensor cu_seqlens, Tensor cu_seqlens_k, int max_seqlen_k) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(llmq_amd, CUDA, m) {
@@ -701,4 +785,5 @@ TORCH_LIBRARY_IMPL(llmq_amd, CUDA, m) {
   m.impl("norm_add_norm", &norm_add_norm);
   m.impl("rope_and_cache", &rope_and_cache);
   m.impl("qknorm_rope_and_cache", &qknorm_rope_and_cache);
+  m.impl("gather_paged_kv", &gather_paged_kv);
 }

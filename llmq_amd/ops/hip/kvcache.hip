@@ -269,3 +269,117 @@ __global__ __launch_bounds__(256) void qknorm_rope_and_cache_kernel(
     }
   }
 }
+
+// ---- paged K/V gather (chunked prefill, prefix-cache hits) -----------------
+// Assembles the packed attention context of a prefill segment: for sequence b
+// with Lq fresh rows and Lk context rows (P = Lk - Lq rows already in the
+// paged cache), context row r comes from cache block block_tables[b, r / bs],
+// row r % bs when r < P, and from fresh row cu_q[b] + r - P otherwise; it
+// lands in packed row cu_k[b] + r of k_out / v_out ([total_k, KVH, D]).
+//
+// A memory-bound copy: no LDS, every global access is 16 bytes. Grid
+// (ceil(max Lk / GATHER_ROWS), B); a workgroup owns GATHER_ROWS consecutive
+// context rows and splits them at P into a past range and a fresh range with
+// workgroup-uniform bounds, so no lane ever chooses between the two sources.
+// Past range: in the cache the rows of one head inside a block are
+// contiguous, so the item index runs head-major with (row, 16-byte piece)
+// fastest; a wave's loads walk one head's run of rows. Fresh range: a row's
+// KVH*D elements are contiguous on both sides, so (row, piece) order.
+//
+// An fp8 cache is widened to T (bf16): a lane loads 16 fp8 bytes and stores
+// two 16-byte vectors. e4m3 -> f32 -> bf16 is exact (3 mantissa bits).
+// All cache offsets are 64-bit: a pool can exceed 2^31 elements.
+
+constexpr int GATHER_ROWS = 16;
+constexpr int GATHER_THREADS = 256;
+
+typedef float gather_f32x2 __attribute__((ext_vector_type(2)));
+
+// 16 bytes of cache at src -> kItem elements of T at dst.
+template <typename T, typename TC>
+DEVINL void gather_copy16(T* __restrict__ dst, const TC* __restrict__ src) {
+  if constexpr (std::is_same_v<T, TC>) {
+    store16(dst, load16(src));
+  } else {  // fp8 cache, bf16 output
+    const int4 raw = *reinterpret_cast<const int4*>(src);
+    const int words[4] = {raw.x, raw.y, raw.z, raw.w};
+#pragma unroll
+    for (int half = 0; half < 2; ++half) {
+      Vec8<T> out;
+#pragma unroll
+      for (int w = 0; w < 2; ++w) {
+        const int word = words[half * 2 + w];
+        const gather_f32x2 lo = __builtin_amdgcn_cvt_pk_f32_fp8(word, false);
+        const gather_f32x2 hi = __builtin_amdgcn_cvt_pk_f32_fp8(word, true);
+        out.data[w * 4 + 0] = from_f32<T>(lo[0]);
+        out.data[w * 4 + 1] = from_f32<T>(lo[1]);
+        out.data[w * 4 + 2] = from_f32<T>(hi[0]);
+        out.data[w * 4 + 3] = from_f32<T>(hi[1]);
+      }
+      store16(dst + half * 8, out);
+    }
+  }
+}
+
+template <typename T, typename TC = T>
+__global__ __launch_bounds__(GATHER_THREADS) void gather_paged_kv_kernel(
+    T* __restrict__ k_out,           // [total_k, kv_heads, D] (row stride out_stride)
+    T* __restrict__ v_out,
+    const TC* __restrict__ k_cache,  // [blocks, kv_heads, bs, D]
+    const TC* __restrict__ v_cache,
+    const T* __restrict__ k_fresh,   // [Tq, kv_heads, D] (row stride kf_stride)
+    const T* __restrict__ v_fresh,
+    const int* __restrict__ block_tables,  // [B, bt_stride]
+    const int* __restrict__ cu_q,          // [B+1]
+    const int* __restrict__ cu_k,          // [B+1]
+    int kv_heads, int head_dim, int block_size, long bt_stride,
+    long ko_stride, long vo_stride, long kf_stride, long vf_stride) {
+  const int b = blockIdx.y;
+  const int q0 = cu_q[b];
+  const int k0 = cu_k[b];
+  const int Lk = cu_k[b + 1] - k0;
+  const int P = Lk - (cu_q[b + 1] - q0);
+  const int r0 = blockIdx.x * GATHER_ROWS;
+  if (r0 >= Lk) return;
+  const int r1 = min(r0 + GATHER_ROWS, Lk);
+
+  // ---- past rows [r0, pe): cache -> out
+  const int pe = min(r1, P);
+  if (r0 < pe) {
+    constexpr int CE = 16 / (int)sizeof(TC);  // cache elements per item
+    const int pieces = head_dim / CE;         // items per (row, head)
+    const int nrows = pe - r0;
+    const int per_head = nrows * pieces;
+    const int items = kv_heads * per_head;
+    const int* bt = block_tables + (long)b * bt_stride;
+    for (int i = threadIdx.x; i < items; i += GATHER_THREADS) {
+      const int h = i / per_head;
+      const int rem = i - h * per_head;
+      const int r = r0 + rem / pieces;
+      const int d = (rem % pieces) * CE;
+      const long block = bt[r / block_size];
+      const long src = ((block * kv_heads + h) * (long)block_size +
+                        (r % block_size)) * head_dim + d;
+      const long col = (long)h * head_dim + d;
+      gather_copy16<T, TC>(k_out + (long)(k0 + r) * ko_stride + col, k_cache + src);
+      gather_copy16<T, TC>(v_out + (long)(k0 + r) * vo_stride + col, v_cache + src);
+    }
+  }
+
+  // ---- fresh rows [fs, r1): this step's k/v -> out
+  const int fs = max(r0, P);
+  if (fs < r1) {
+    constexpr int VE = Vec8<T>::kElems;
+    const int pieces = (kv_heads * head_dim) / VE;  // items per row
+    const int items = (r1 - fs) * pieces;
+    for (int i = threadIdx.x; i < items; i += GATHER_THREADS) {
+      const int r = fs + i / pieces;
+      const long col = (long)(i % pieces) * VE;
+      const long srow = (long)(q0 + r - P);
+      store16(k_out + (long)(k0 + r) * ko_stride + col,
+              load16(k_fresh + srow * kf_stride + col));
+      store16(v_out + (long)(k0 + r) * vo_stride + col,
+              load16(v_fresh + srow * vf_stride + col));
+    }
+  }
+}

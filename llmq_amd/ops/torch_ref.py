@@ -127,6 +127,48 @@ def reshape_and_cache(
     v_cache[blocks, :, offs, :] = value.to(v_cache.dtype)
 
 
+def gather_paged_kv(
+    k_out: torch.Tensor,  # [>= total_k, kv_heads, head_dim]
+    v_out: torch.Tensor,
+    k_cache: torch.Tensor,  # [num_blocks, kv_heads, block_size, head_dim]
+    v_cache: torch.Tensor,
+    k_fresh: torch.Tensor,  # [Tq, kv_heads, head_dim] (may be strided views)
+    v_fresh: torch.Tensor,
+    block_tables: torch.Tensor,  # [B, W] int32
+    cu_seqlens: torch.Tensor,    # [B+1] int32 fresh-row offsets
+    cu_seqlens_k: torch.Tensor,  # [B+1] int32 context-row offsets
+    max_seqlen_k: int,
+) -> None:
+    """Packed attention context per sequence: P = Lk - Lq rows gathered from
+    the paged cache through the sequence's block table, then its Lq fresh
+    rows, written to rows [cu_seqlens_k[b], cu_seqlens_k[b+1]) of k_out /
+    v_out. Cache rows are cast to the output dtype (fp8 → bf16 is exact)."""
+    B = cu_seqlens.numel() - 1
+    if B == 0 or max_seqlen_k == 0:
+        return
+    dev = k_out.device
+    bs = k_cache.shape[2]
+    cu_q = cu_seqlens.long()
+    cu_k = cu_seqlens_k.long()
+    total_k = int(cu_k[-1])
+    lens_k = cu_k[1:] - cu_k[:-1]
+    past = lens_k - (cu_q[1:] - cu_q[:-1])                      # [B]
+    rows = torch.arange(total_k, device=dev)
+    seq = torch.repeat_interleave(torch.arange(B, device=dev), lens_k)
+    r = rows - cu_k[seq]                                        # row in context
+    is_past = r < past[seq]
+    # past rows: cache[block_tables[b, r // bs], :, r % bs]
+    pr, ps = r[is_past], seq[is_past]
+    blocks = block_tables.long()[ps, pr // bs]
+    k_out[rows[is_past]] = k_cache[blocks, :, pr % bs].to(k_out.dtype)
+    v_out[rows[is_past]] = v_cache[blocks, :, pr % bs].to(v_out.dtype)
+    # fresh rows: k_fresh[cu_seqlens[b] + r - P]
+    fr, fsq = r[~is_past], seq[~is_past]
+    src = cu_q[fsq] + fr - past[fsq]
+    k_out[rows[~is_past]] = k_fresh[src]
+    v_out[rows[~is_past]] = v_fresh[src]
+
+
 def qknorm_rope_and_cache(
     q: torch.Tensor,  # [T, num_heads, head_dim]
     k: torch.Tensor,  # [T, num_kv_heads, head_dim]

@@ -55,6 +55,7 @@ class _FinishedRequest:
     queue_wait_ms: Optional[float]
     prefill_ms: Optional[float]
     decode_ms: Optional[float]
+    cached_tokens: int = 0
 
 
 @dataclass
@@ -204,6 +205,8 @@ class AsyncEngineBridge:
                                 queue_wait_ms=out.queue_wait_ms,
                                 prefill_ms=out.prefill_ms,
                                 decode_ms=out.decode_ms,
+                                # engines without a prefix cache report none
+                                cached_tokens=getattr(out, "cached_tokens", 0),
                             ),
                         )
         except BaseException as exc:  # noqa: BLE001 — engine died: fail fast
@@ -351,6 +354,8 @@ class EngineWorker(BaseWorker):
         max_len = self._max_model_len or self.config.max_model_len
         if max_len:
             kwargs["max_model_len"] = max_len
+        if self.config.enable_prefix_caching:
+            kwargs["enable_prefix_caching"] = True
         kwargs.update(self.engine_overrides)
         return kwargs
 
@@ -461,6 +466,7 @@ class EngineWorker(BaseWorker):
         stats = self._stats.pop(job.id, None)
         if stats is not None:
             result.prompt_tokens = stats.prompt_tokens
+            result.cached_tokens = stats.cached_tokens
             result.output_tokens = stats.output_tokens
             result.finish_reason = stats.finish_reason
             result.queue_wait_ms = stats.queue_wait_ms
