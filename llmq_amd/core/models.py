@@ -25,6 +25,10 @@ _CONTROL_FIELDS = (
     "top_k",
     "max_tokens",
     "seed",
+    "repetition_penalty",
+    "presence_penalty",
+    "frequency_penalty",
+    "min_p",
 )
 
 
@@ -48,6 +52,10 @@ class Job(BaseModel):
     top_k: Optional[int] = Field(None)
     max_tokens: Optional[int] = Field(None)
     seed: Optional[int] = Field(None)
+    repetition_penalty: Optional[float] = Field(None)
+    presence_penalty: Optional[float] = Field(None)
+    frequency_penalty: Optional[float] = Field(None)
+    min_p: Optional[float] = Field(None)
 
     @model_validator(mode="after")
     def _exactly_one_input(self) -> "Job":

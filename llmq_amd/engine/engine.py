@@ -26,6 +26,7 @@ from llmq_amd.engine.config import EngineConfig
 from llmq_amd.engine.kv_cache import BlockAllocator, KVCache, PrefixCachingAllocator
 from llmq_amd.engine.model_runner import ModelRunner
 from llmq_amd.engine.model_specs import ModelSpec, resolve_spec
+from llmq_amd.engine.penalty_table import wants_penalties
 from llmq_amd.engine.models.llama import CausalLM
 from llmq_amd.engine.sampling_params import SamplingParams
 from llmq_amd.engine.scheduler import Scheduler, Sequence
@@ -181,6 +182,8 @@ class LLMEngine:
                 else overlap_default
             )
         )
+        # finish, abort and preemption give a sequence's penalty-table row back
+        self.scheduler.on_release = self.runner.penalty_table.release
         self._decode_stream = (
             torch.cuda.Stream(device=self.device) if self._overlap_mixed else None
         )
@@ -281,13 +284,20 @@ class LLMEngine:
             prompt_token_ids = self.tokenizer.encode(prompt)
         if not prompt_token_ids:
             prompt_token_ids = [self.spec.bos_token_id]
+        if self.device.type == "cuda" and wants_penalties(params):
+            # The count table is allocated with the first penalised request,
+            # here and not inside a step, so that running out of memory
+            # (PenaltyTableError, a ValueError) fails this request alone.
+            self.runner.penalty_table.ensure_allocated()
         seq = Sequence(request_id, prompt_token_ids, params, arrival_time=time.time())
         self._seqs[request_id] = seq
         self.scheduler.add(seq)
 
     def abort_request(self, request_id: str) -> None:
         self.scheduler.abort(request_id)
-        self._seqs.pop(request_id, None)
+        seq = self._seqs.pop(request_id, None)
+        if seq is not None:
+            self.runner.penalty_table.release(seq)
         self._prefill_done_at.pop(request_id, None)
 
     def prefix_cache_stats(self) -> Dict[str, int]:

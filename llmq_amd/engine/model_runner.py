@@ -25,6 +25,10 @@ from llmq_amd.engine.forward_meta import (
 )
 from llmq_amd.engine.kv_cache import KVCache, blocks_needed
 from llmq_amd.engine.models.llama import CausalLM
+from llmq_amd.engine.penalty_table import (
+    COUNT_MASK, PROMPT_BIT, PenaltyTable, count_words, wants_penalties,
+)
+from llmq_amd.ops import torch_ref
 from llmq_amd.engine.scheduler import ScheduledBatch, Sequence
 
 logger = logging.getLogger(__name__)
@@ -67,6 +71,10 @@ class ModelRunner:
         # decode path, "prefill" for the prefill segment of an OVERLAPPED
         # split mixed step — two concurrent streams must not share them).
         self._sample_bufs: Dict[str, Dict[str, torch.Tensor]] = {}
+        # Count table of the repetition/presence/frequency penalties; holds no
+        # memory until the first penalised request (PenaltyTable docstring).
+        self.penalty_table = PenaltyTable(
+            config.max_num_seqs, model.spec.vocab_size, device)
         # GPU logit tail: the sampler kernels read the lm_head GEMM's output
         # in the model dtype and apply the final soft-cap in registers, so no
         # fp32 [B, vocab] matrix is ever materialised. LLMQ_FUSED_LOGIT_TAIL=0
@@ -400,6 +408,12 @@ class ModelRunner:
                 "seeds_h": torch.empty(cap, dtype=torch.int32, pin_memory=True),
                 "pos": torch.empty(cap, dtype=torch.int32, device=dev),
                 "pos_h": torch.empty(cap, dtype=torch.int32, pin_memory=True),
+                "minp": torch.empty(cap, dtype=torch.float32, device=dev),
+                "minp_h": torch.empty(cap, dtype=torch.float32, pin_memory=True),
+                "slots": torch.empty(cap, dtype=torch.int32, device=dev),
+                "slots_h": torch.empty(cap, dtype=torch.int32, pin_memory=True),
+                "pen": torch.empty(cap, 3, dtype=torch.float32, device=dev),
+                "pen_h": torch.empty(cap, 3, dtype=torch.float32, pin_memory=True),
             }
             self._sample_bufs[name] = buf
         return buf
@@ -413,13 +427,29 @@ class ModelRunner:
             return self.model.lm_head_logits(hidden), float(cap) if cap and cap > 0 else 0.0
         return self.model.compute_logits(hidden), 0.0
 
+    @staticmethod
+    def _penalised_logits_cpu(logits: torch.Tensor, seqs: List[Sequence]) -> torch.Tensor:
+        V = logits.size(1)
+        words = torch.from_numpy(np.stack([
+            count_words(s.token_ids, s.prompt_len, V).astype(np.int32) for s in seqs
+        ]))
+        p = [s.params for s in seqs]
+        return torch_ref.apply_penalties(
+            logits, words & COUNT_MASK, (words & PROMPT_BIT) != 0,
+            torch.tensor([q.repetition_penalty for q in p]),
+            torch.tensor([q.frequency_penalty for q in p]),
+            torch.tensor([q.presence_penalty for q in p]),
+        )
+
     def _sample(self, logits: torch.Tensor, seqs: List[Sequence],
                 buf_name: str = "main", softcap: float = 0.0) -> torch.Tensor:
         dev = logits.device
         self._sample_step += 1
         simple = all(
-            s.params.top_k == 0 and s.params.top_p >= 1.0 for s in seqs
+            s.params.top_k == 0 and s.params.top_p >= 1.0 and s.params.min_p <= 0.0
+            for s in seqs
         )
+        penalised = any(wants_penalties(s.params) for s in seqs)
         if dev.type == "cuda":
             # Fused one-pass HIP sampler (gumbel-max / greedy argmax).
             # Top-k/top-p rows reduce to a per-row logit keep-bound via
@@ -444,25 +474,56 @@ class ModelRunner:
             buf["pos"][:B].copy_(ph[:B], non_blocking=True)
             # fused tail: logits stay in the GEMM's dtype (no fp32 copy)
             logits_f = logits if self.fused_logit_tail else logits.float()
+            # Penalised rows read their row of the count table inside the
+            # kernels; a batch without any passes no table and runs the
+            # kernels it ran before the table existed.
+            pen = {}
+            if penalised:
+                slots = self.penalty_table.slots_for(seqs)
+                slh, pnh = buf["slots_h"], buf["pen_h"]
+                for i, s in enumerate(seqs):
+                    slh[i] = slots[i]
+                    pnh[i, 0] = s.params.repetition_penalty
+                    pnh[i, 1] = s.params.frequency_penalty
+                    pnh[i, 2] = s.params.presence_penalty
+                buf["slots"][:B].copy_(slh[:B], non_blocking=True)
+                buf["pen"][:B].copy_(pnh[:B], non_blocking=True)
+                pen = dict(pen_table=self.penalty_table.table,
+                           pen_slots=buf["slots"][:B], pen_params=buf["pen"][:B])
             bounds = None
             if not simple:
                 tps = torch.tensor([s.params.top_p for s in seqs],
                                    dtype=torch.float32, device=dev)
                 tks = torch.tensor([s.params.top_k for s in seqs],
                                    dtype=torch.int64, device=dev)
+                min_ps = None
+                if any(s.params.min_p > 0.0 for s in seqs):
+                    mh = buf["minp_h"]
+                    for i, s in enumerate(seqs):
+                        mh[i] = s.params.min_p
+                    buf["minp"][:B].copy_(mh[:B], non_blocking=True)
+                    min_ps = buf["minp"][:B]
                 bounds = ops.topk_topp_bound(
-                    logits_f, buf["temps"][:B], tps, tks, softcap)
+                    logits_f, buf["temps"][:B], tps, tks, softcap,
+                    min_ps=min_ps, **pen)
             ops.sample_gumbel_argmax(
                 buf["out"][:B], buf["keys"][:B], logits_f,
                 buf["temps"][:B], buf["seeds"][:B],
                 buf["pos"][:B], self.config.seed, self._sample_step, bounds,
-                softcap,
+                softcap, **pen,
             )
+            if penalised:
+                self.penalty_table.count_sampled(
+                    seqs, buf["slots"][:B], buf["out"][:B])
             return buf["out"][:B]
+        if penalised:
+            # CPU: the specification itself, from the token histories
+            logits = self._penalised_logits_cpu(logits, seqs)
         temps = torch.tensor([s.params.temperature for s in seqs], dtype=torch.float32, device=dev)
         tps = torch.tensor([s.params.top_p for s in seqs], dtype=torch.float32, device=dev)
         tks = torch.tensor([s.params.top_k for s in seqs], dtype=torch.int64, device=dev)
-        out = ops.sample_tokens(logits, temps, tps, tks, self.sampling_generator)
+        mps = torch.tensor([s.params.min_p for s in seqs], dtype=torch.float32, device=dev)
+        out = ops.sample_tokens(logits, temps, tps, tks, self.sampling_generator, mps)
         # Per-request seeds (reproducible sampling): re-draw those rows with
         # a generator keyed on (seed, output position) — batch-independent.
         # Gathered in ONE device→host transfer (a per-row .cpu() would sync
@@ -475,6 +536,7 @@ class ModelRunner:
             idx = torch.tensor(seeded, dtype=torch.long, device=dev)
             rows = logits[idx].float().cpu()
             temps_c, tps_c, tks_c = temps[idx].cpu(), tps[idx].cpu(), tks[idx].cpu()
+            mps_c = mps[idx].cpu()
             redraw = torch.empty(len(seeded), dtype=out.dtype)
             for j, i in enumerate(seeded):
                 s = seqs[i]
@@ -482,7 +544,7 @@ class ModelRunner:
                 g.manual_seed((s.params.seed << 20) ^ s.output_len)
                 redraw[j] = ops.sample_tokens(
                     rows[j : j + 1], temps_c[j : j + 1], tps_c[j : j + 1],
-                    tks_c[j : j + 1], g,
+                    tks_c[j : j + 1], g, mps_c[j : j + 1],
                 )[0]
             out[idx] = redraw.to(out.device)
         return out

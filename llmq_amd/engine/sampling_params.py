@@ -19,6 +19,15 @@ class SamplingParams:
     stop: Optional[List[str]] = None
     seed: Optional[int] = None
     ignore_eos: bool = False
+    # Applied by the sampler to the (soft-capped) logits in this order:
+    # tokens seen in the prompt or the output: l > 0 ? l / r : l * r; then
+    # l -= frequency_penalty * count_in_output; then l -= presence_penalty
+    # for tokens in the output. Greedy rows take the argmax of the result.
+    repetition_penalty: float = 1.0  # 1 = off
+    presence_penalty: float = 0.0
+    frequency_penalty: float = 0.0
+    # keep tokens with probability >= min_p x the most likely token's
+    min_p: float = 0.0  # 0 = off
 
     def __post_init__(self) -> None:
         if self.temperature < 0:
@@ -29,6 +38,14 @@ class SamplingParams:
             raise ValueError("top_k must be >= 0")
         if self.max_tokens < 1:
             raise ValueError("max_tokens must be >= 1")
+        if not self.repetition_penalty > 0:
+            raise ValueError("repetition_penalty must be > 0")
+        if not -2.0 <= self.presence_penalty <= 2.0:
+            raise ValueError("presence_penalty must be in [-2, 2]")
+        if not -2.0 <= self.frequency_penalty <= 2.0:
+            raise ValueError("frequency_penalty must be in [-2, 2]")
+        if not 0.0 <= self.min_p <= 1.0:
+            raise ValueError("min_p must be in [0, 1]")
 
     @property
     def greedy(self) -> bool:

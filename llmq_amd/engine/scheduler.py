@@ -25,7 +25,7 @@ import logging
 from collections import deque
 from dataclasses import dataclass, field
 from enum import Enum
-from typing import Deque, List, Optional
+from typing import Callable, Deque, List, Optional
 
 from llmq_amd.engine.kv_cache import BlockAllocator, blocks_needed
 from llmq_amd.engine.sampling_params import SamplingParams
@@ -119,6 +119,9 @@ class Scheduler:
         self.prefilling: List[Sequence] = []
         # PrefixCachingAllocator: admission looks up the prompt's head first
         self.prefix_caching = hasattr(allocator, "lookup")
+        # called with every sequence whose KV blocks are released (finish,
+        # abort, preemption): the engine frees per-sequence sampler state
+        self.on_release: Optional[Callable[[Sequence], None]] = None
 
     # -- public ----------------------------------------------------------
 
@@ -287,6 +290,8 @@ class Scheduler:
         self.allocator.register(seq.token_ids, seq.block_table, end)
 
     def _release(self, seq: Sequence) -> None:
+        if self.on_release is not None:
+            self.on_release(seq)
         if seq.block_table:
             self.allocator.free(seq.block_table)
             seq.block_table = []

@@ -340,6 +340,9 @@ def sample_gumbel_argmax(
     step: int,
     bounds: Optional[torch.Tensor] = None,  # [B] fp32 top-k/p keep-bound
     softcap: float = 0.0,     # > 0: sample from cap * tanh(logit / cap)
+    pen_table: Optional[torch.Tensor] = None,   # [slots, Vpad] int16 counts
+    pen_slots: Optional[torch.Tensor] = None,   # [B] int32 table row (-1 = none)
+    pen_params: Optional[torch.Tensor] = None,  # [B, 3] fp32 (r, freq, pres)
 ) -> None:
     """Fused one-pass sampler: per-row Gumbel-max (== softmax sampling) or
     argmax for greedy rows, optionally truncated to {logit >= bounds[b]}
@@ -348,11 +351,15 @@ def sample_gumbel_argmax(
     draw from (request_seed, output_position) — reproducible for a given
     request regardless of batch placement. The kernel widens the logits and
     applies the final soft-cap in registers: tokens equal those sampled from
-    `torch.tanh(logits.float() / softcap) * softcap`."""
+    `torch.tanh(logits.float() / softcap) * softcap`. With a count table,
+    rows whose slot is >= 0 sample from `torch_ref.apply_penalties` of those
+    logits (bit 15 of a table word = in the prompt, bits 0-14 = output
+    count); without one the call runs the kernel it ran before."""
     assert _use_hip(logits)
     keys.zero_()
     _EXT.sample_gumbel_argmax(out, keys, logits, temps, req_seeds, req_pos,
-                              seed, step, bounds, softcap)
+                              seed, step, bounds, softcap, pen_table,
+                              pen_slots, pen_params)
 
 
 def topk_topp_bound(
@@ -361,15 +368,41 @@ def topk_topp_bound(
     top_ps: torch.Tensor,   # [B] fp32
     top_ks: torch.Tensor,   # [B] int64 (0 = off)
     softcap: float = 0.0,   # > 0: bound on cap * tanh(logit / cap)
+    min_ps: Optional[torch.Tensor] = None,      # [B] fp32 (0 = off)
+    pen_table: Optional[torch.Tensor] = None,   # as in sample_gumbel_argmax
+    pen_slots: Optional[torch.Tensor] = None,
+    pen_params: Optional[torch.Tensor] = None,
 ) -> torch.Tensor:
     """Per-row logit-space keep-bound realising top-p ∧ top-k truncation
     via histogram select (3 streaming passes; no full-vocab sort). With a
     soft-cap the bound is in capped-logit space, the space the sampler
-    compares in when given the same `softcap`."""
+    compares in when given the same `softcap`. min_p adds the bound
+    max + T * ln(min_p); a row keeps the larger of the two bounds. With a
+    count table the bound is on the penalised logits."""
     assert _use_hip(logits)
     out = torch.empty(logits.size(0), dtype=torch.float32, device=logits.device)
-    _EXT.topk_topp_bound(out, logits, temps, top_ps, top_ks, softcap)
+    _EXT.topk_topp_bound(out, logits, temps, top_ps, top_ks, softcap, min_ps,
+                         pen_table, pen_slots, pen_params)
     return out
+
+
+def penalty_count_tokens(
+    table: torch.Tensor,   # [slots, Vpad] int16 counts
+    slots: torch.Tensor,   # [B] int32 (-1 = none); distinct where >= 0
+    tokens: torch.Tensor,  # [B] int64 sampled tokens
+) -> None:
+    """table[slots[b], tokens[b]] += 1 on bits 0-14 (saturating at 32767, bit
+    15 kept) for rows with a slot. On the GPU one kernel on the current
+    stream; on CPU tensors the same update with torch ops."""
+    if _use_hip(table):
+        _EXT.penalty_count_tokens(table, slots, tokens)
+        return
+    rows = (slots >= 0).nonzero(as_tuple=True)[0]
+    if rows.numel() == 0:
+        return
+    s, t = slots[rows].long(), tokens[rows].long()
+    words = table[s, t]
+    table.index_put_((s, t), torch.where((words & 0x7FFF) == 0x7FFF, words, words + 1))
 
 
 def sample_tokens(
@@ -378,12 +411,13 @@ def sample_tokens(
     top_ps: torch.Tensor,
     top_ks: torch.Tensor,
     generator: Optional[torch.Generator] = None,
+    min_p: Optional[torch.Tensor] = None,
 ) -> torch.Tensor:
-    # Generic path (top-k/top-p capable). The serving hot loop uses the
+    # Generic path (top-k/top-p/min_p capable). The serving hot loop uses the
     # fused sample_gumbel_argmax above when no top-k/top-p is requested.
     if logits.is_cuda:
-        return _sample_tokens_gpu(logits, temperatures, top_ps, top_ks, generator)
-    return torch_ref.sample_tokens(logits, temperatures, top_ps, top_ks, generator)
+        return _sample_tokens_gpu(logits, temperatures, top_ps, top_ks, generator, min_p)
+    return torch_ref.sample_tokens(logits, temperatures, top_ps, top_ks, generator, min_p)
 
 
 def _sample_tokens_gpu(
@@ -392,6 +426,7 @@ def _sample_tokens_gpu(
     top_ps: torch.Tensor,
     top_ks: torch.Tensor,
     generator: Optional[torch.Generator],
+    min_p: Optional[torch.Tensor] = None,
 ) -> torch.Tensor:
     """Batched GPU sampling without per-sequence python loops."""
     B, V = logits.shape
@@ -400,11 +435,13 @@ def _sample_tokens_gpu(
     scaled = logits.float() / temps.unsqueeze(1)
     need_topk = bool((top_ks > 0).any()) and bool((top_ks < V).any())
     need_topp = bool((top_ps < 1.0).any())
-    if need_topk or need_topp:
+    need_minp = min_p is not None and bool((min_p > 0).any())
+    if need_topk or need_topp or need_minp:
         # histogram-select keep-bound (3 streaming passes) instead of the
         # full-vocab sort — at B=256 × V=256k the sort was a multi-ms cliff
         bound = topk_topp_bound(logits.float(), temperatures.float(),
-                                top_ps.float(), top_ks)
+                                top_ps.float(), top_ks,
+                                min_ps=min_p.float() if need_minp else None)
         scaled = torch.where(logits.float() >= bound.unsqueeze(1), scaled,
                              torch.full_like(scaled, float("-inf")))
     # Gumbel-max trick: single fused sample, no multinomial sync.

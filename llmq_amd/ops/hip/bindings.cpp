@@ -689,8 +689,49 @@ float softcap_reciprocal(double softcap) {
   return softcap > 0 ? 1.0f / (float)softcap : 0.0f;
 }
 
+// The penalty arguments of the two sampler ops: the count table [nslots, vpad]
+// (int16, read as unsigned), a per-row int32 slot (-1 = none) and per-row
+// fp32 (r, freq, pres). All three or none.
+struct PenaltyArgs {
+  const unsigned short* table = nullptr;
+  const int* slots = nullptr;
+  const float* params = nullptr;
+  int nslots = 0;
+  long vpad = 0;
+};
+
+PenaltyArgs penalty_args(const c10::optional<at::Tensor>& table,
+                         const c10::optional<at::Tensor>& slots,
+                         const c10::optional<at::Tensor>& params, int B, int V) {
+  PenaltyArgs a;
+  const bool has = table.has_value() && table->defined();
+  TORCH_CHECK(has == (slots.has_value() && slots->defined()) &&
+                  has == (params.has_value() && params->defined()),
+              "pen_table, pen_slots and pen_params go together");
+  if (!has) return a;
+  CHECK_GPU((*table));
+  CHECK_GPU((*slots));
+  CHECK_GPU((*params));
+  TORCH_CHECK(table->scalar_type() == at::kShort && table->dim() == 2 &&
+              table->is_contiguous() && table->size(1) >= V);
+  TORCH_CHECK(slots->scalar_type() == at::kInt && slots->is_contiguous() &&
+              slots->numel() == B);
+  TORCH_CHECK(params->scalar_type() == at::kFloat && params->is_contiguous() &&
+              params->dim() == 2 && params->size(0) == B && params->size(1) == 3);
+  a.table = reinterpret_cast<const unsigned short*>(table->data_ptr());
+  a.slots = slots->data_ptr<int>();
+  a.params = params->data_ptr<float>();
+  a.nslots = table->size(0);
+  a.vpad = table->size(1);
+  return a;
+}
+
 void topk_topp_bound(at::Tensor out_bound, at::Tensor logits, at::Tensor temps,
-                     at::Tensor top_ps, at::Tensor top_ks, double softcap) {
+                     at::Tensor top_ps, at::Tensor top_ks, double softcap,
+                     c10::optional<at::Tensor> min_ps,
+                     c10::optional<at::Tensor> pen_table,
+                     c10::optional<at::Tensor> pen_slots,
+                     c10::optional<at::Tensor> pen_params) {
   CHECK_GPU(logits);
   CHECK_LASTDIM(logits);
   TORCH_CHECK(logits.dim() == 2);
@@ -699,21 +740,41 @@ void topk_topp_bound(at::Tensor out_bound, at::Tensor logits, at::Tensor temps,
   TORCH_CHECK(top_ps.scalar_type() == at::kFloat);
   TORCH_CHECK(top_ks.scalar_type() == at::kLong);
   const int B = logits.size(0), V = logits.size(1);
+  TORCH_CHECK(out_bound.numel() == B && temps.numel() == B &&
+              top_ps.numel() == B && top_ks.numel() == B);
+  const float* min_ps_ptr = nullptr;
+  if (min_ps.has_value() && min_ps->defined()) {
+    CHECK_GPU((*min_ps));
+    TORCH_CHECK(min_ps->scalar_type() == at::kFloat && min_ps->numel() == B &&
+                min_ps->is_contiguous());
+    min_ps_ptr = min_ps->data_ptr<float>();
+  }
+  const PenaltyArgs pen = penalty_args(pen_table, pen_slots, pen_params, B, V);
   if (B == 0) return;
   dispatch_dtype(logits, "topk_topp_bound", [&]<typename T>() {
-    hipLaunchKernelGGL(topk_topp_bound_kernel<T>, dim3(B), dim3(256), 0,
-                       stream(), out_bound.data_ptr<float>(),
-                       reinterpret_cast<const T*>(logits.data_ptr()),
-                       temps.data_ptr<float>(), top_ps.data_ptr<float>(),
-                       top_ks.data_ptr<long>(), V, logits.stride(0),
-                       (float)softcap, softcap_reciprocal(softcap));
+    auto launch = [&](auto kernel) {
+      hipLaunchKernelGGL(kernel, dim3(B), dim3(256), 0, stream(),
+                         out_bound.data_ptr<float>(),
+                         reinterpret_cast<const T*>(logits.data_ptr()),
+                         temps.data_ptr<float>(), top_ps.data_ptr<float>(),
+                         top_ks.data_ptr<long>(), V, logits.stride(0),
+                         (float)softcap, softcap_reciprocal(softcap),
+                         min_ps_ptr, pen.table, pen.slots, pen.params,
+                         pen.nslots, pen.vpad);
+    };
+    // without min_p and penalties: the kernel as it was before it had them
+    if (min_ps_ptr || pen.table) launch(topk_topp_bound_kernel<T, true>);
+    else launch(topk_topp_bound_kernel<T, false>);
   });
 }
 
 void sample_gumbel_argmax(at::Tensor out, at::Tensor keys, at::Tensor logits,
                           at::Tensor temps, at::Tensor req_seeds,
                           at::Tensor req_pos, long seed, long step,
-                          c10::optional<at::Tensor> bounds, double softcap) {
+                          c10::optional<at::Tensor> bounds, double softcap,
+                          c10::optional<at::Tensor> pen_table,
+                          c10::optional<at::Tensor> pen_slots,
+                          c10::optional<at::Tensor> pen_params) {
   CHECK_GPU(logits);
   CHECK_LASTDIM(logits);
   TORCH_CHECK(logits.dim() == 2);
@@ -728,6 +789,7 @@ void sample_gumbel_argmax(at::Tensor out, at::Tensor keys, at::Tensor logits,
     TORCH_CHECK(bounds->scalar_type() == at::kFloat && bounds->numel() == B);
     bounds_ptr = bounds->data_ptr<float>();
   }
+  const PenaltyArgs pen = penalty_args(pen_table, pen_slots, pen_params, B, V);
   // enough splits to fill the chip at small B
   int nsplit = 1;
   while (B * nsplit < 2048 && nsplit < 64 && (V / nsplit) > 4096) nsplit *= 2;
@@ -735,19 +797,45 @@ void sample_gumbel_argmax(at::Tensor out, at::Tensor keys, at::Tensor logits,
   // boundary of its row and is all vector loads
   const int chunk = ((V + nsplit - 1) / nsplit + 7) / 8 * 8;
   dispatch_dtype(logits, "sample_gumbel_argmax", [&]<typename T>() {
-    hipLaunchKernelGGL(
-        sample_argmax_kernel<T>, dim3(B, nsplit), dim3(256), 0, stream(),
-        reinterpret_cast<unsigned long long*>(keys.data_ptr()),
-        reinterpret_cast<const T*>(logits.data_ptr()), temps.data_ptr<float>(),
-        reinterpret_cast<const unsigned int*>(req_seeds.data_ptr()),
-        reinterpret_cast<const unsigned int*>(req_pos.data_ptr()), bounds_ptr,
-        V, logits.stride(0), chunk, (float)softcap,
-        softcap_reciprocal(softcap), (unsigned int)seed, (unsigned int)step);
+    auto launch = [&](auto kernel) {
+      hipLaunchKernelGGL(
+          kernel, dim3(B, nsplit), dim3(256), 0, stream(),
+          reinterpret_cast<unsigned long long*>(keys.data_ptr()),
+          reinterpret_cast<const T*>(logits.data_ptr()), temps.data_ptr<float>(),
+          reinterpret_cast<const unsigned int*>(req_seeds.data_ptr()),
+          reinterpret_cast<const unsigned int*>(req_pos.data_ptr()), bounds_ptr,
+          V, logits.stride(0), chunk, (float)softcap,
+          softcap_reciprocal(softcap), (unsigned int)seed, (unsigned int)step,
+          pen.table, pen.slots, pen.params, pen.nslots, pen.vpad);
+    };
+    // without a table: the kernel as it was before it had penalties
+    if (pen.table) launch(sample_argmax_kernel<T, true>);
+    else launch(sample_argmax_kernel<T, false>);
   });
   hipLaunchKernelGGL(unpack_keys_kernel, dim3((B + 255) / 256), dim3(256), 0,
                      stream(), out.data_ptr<long>(),
                      reinterpret_cast<const unsigned long long*>(keys.data_ptr()),
                      B);
+}
+
+// Adds the tokens just sampled to their rows' output counts, on the current
+// stream, reading the token tensor on the device.
+void penalty_count_tokens(at::Tensor table, at::Tensor slots, at::Tensor tokens) {
+  CHECK_GPU(table);
+  CHECK_GPU(slots);
+  CHECK_GPU(tokens);
+  TORCH_CHECK(table.scalar_type() == at::kShort && table.dim() == 2 &&
+              table.is_contiguous());
+  TORCH_CHECK(slots.scalar_type() == at::kInt && slots.is_contiguous());
+  TORCH_CHECK(tokens.scalar_type() == at::kLong && tokens.is_contiguous() &&
+              tokens.numel() == slots.numel());
+  const int B = slots.numel();
+  if (B == 0) return;
+  hipLaunchKernelGGL(penalty_count_tokens_kernel, dim3((B + 255) / 256),
+                     dim3(256), 0, stream(),
+                     reinterpret_cast<unsigned short*>(table.data_ptr()),
+                     slots.data_ptr<int>(), tokens.data_ptr<long>(), B,
+                     (int)table.size(0), (long)table.size(1));
 }
 
 }  // namespace
@@ -761,8 +849,9 @@ TORCH_LIBRARY(llmq_amd, m) {
   m.def("reshape_and_cache(Tensor key, Tensor value, Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor slot_mapping) -> ()");
   m.def("paged_decode_attention(Tensor(a!) out, Tensor q, Tensor k_cache, Tensor v_cache, Tensor block_tables, Tensor context_lens, float scale, float softcap, int window) -> ()");
   m.def("varlen_prefill_attention(Tensor(a!) out, Tensor q, Tensor k, Tensor v, Tensor cu_seqlens, Tensor cu_seqlens_k, int max_seqlen, float scale, float softcap, int window) -> ()");
-  m.def("sample_gumbel_argmax(Tensor(a!) out, Tensor(b!) keys, Tensor logits, Tensor temps, Tensor req_seeds, Tensor req_pos, int seed, int step, Tensor? bounds=None, float softcap=0.0) -> ()");
-  m.def("topk_topp_bound(Tensor(a!) out_bound, Tensor logits, Tensor temps, Tensor top_ps, Tensor top_ks, float softcap=0.0) -> ()");
+  m.def("sample_gumbel_argmax(Tensor(a!) out, Tensor(b!) keys, Tensor logits, Tensor temps, Tensor req_seeds, Tensor req_pos, int seed, int step, Tensor? bounds=None, float softcap=0.0, Tensor? pen_table=None, Tensor? pen_slots=None, Tensor? pen_params=None) -> ()");
+  m.def("topk_topp_bound(Tensor(a!) out_bound, Tensor logits, Tensor temps, Tensor top_ps, Tensor top_ks, float softcap=0.0, Tensor? min_ps=None, Tensor? pen_table=None, Tensor? pen_slots=None, Tensor? pen_params=None) -> ()");
+  m.def("penalty_count_tokens(Tensor(a!) table, Tensor slots, Tensor tokens) -> ()");
   m.def("skinny_gemm(Tensor(a!) out, Tensor x, Tensor w, Tensor? bias, int splitk) -> ()");
   m.def("norm_add_norm(Tensor(a!) x, Tensor(b!) residual, Tensor w_post, Tensor w_pre, float eps, float offset) -> ()");
   m.def("rope_and_cache(Tensor(a!) q, Tensor(b!) k, Tensor value, Tensor(c!) k_cache, Tensor(d!) v_cache, Tensor positions, Tensor cos_sin, Tensor slot_mapping) -> ()");
@@ -781,6 +870,7 @@ TORCH_LIBRARY_IMPL(llmq_amd, CUDA, m) {
   m.impl("varlen_prefill_attention", &varlen_prefill_attention);
   m.impl("sample_gumbel_argmax", &sample_gumbel_argmax);
   m.impl("topk_topp_bound", &topk_topp_bound);
+  m.impl("penalty_count_tokens", &penalty_count_tokens);
   m.impl("skinny_gemm", &skinny_gemm);
   m.impl("norm_add_norm", &norm_add_norm);
   m.impl("rope_and_cache", &rope_and_cache);

@@ -15,6 +15,8 @@
 // step, independent of launch geometry, so eager and hipGraph runs sample
 // identical tokens.
 
+#include <type_traits>
+
 #include "common.h"
 
 DEVINL unsigned int hash_u32(unsigned int x) {
@@ -64,6 +66,42 @@ DEVINL float logit_value(T raw, float softcap, float inv_cap) {
   return x;
 }
 
+// Sampling penalties. A penalised row has a row of the dense count table
+// [slots, vpad]: one unsigned 16-bit word per vocab entry, bit 15 = "occurs
+// in the prompt", bits 0-14 = occurrences in the output so far (saturating
+// at 32767). Applied to the capped fp32 logit in the order of
+// torch_ref.apply_penalties, with a true division and contraction off, so
+// the result equals the torch expression bit for bit:
+//   seen = in_prompt | (c > 0);  l = seen ? (l > 0 ? l / r : l * r) : l
+//   l = l - freq * float(c);     l = l - pres * float(c > 0)
+struct PenaltyRow {
+  const unsigned short* cnt;  // the row's counts, or null: row not penalised
+  float r, freq, pres;
+};
+
+DEVINL PenaltyRow penalty_row(const unsigned short* table, const int* slots,
+                              const float* params, int nslots, long vpad,
+                              int b) {
+  PenaltyRow p{nullptr, 1.0f, 0.0f, 0.0f};
+  if (!table) return p;
+  const int slot = slots[b];
+  if (slot < 0 || slot >= nslots) return p;
+  p.cnt = table + (long)slot * vpad;
+  p.r = params[3 * b];
+  p.freq = params[3 * b + 1];
+  p.pres = params[3 * b + 2];
+  return p;
+}
+
+DEVINL float penalize(float l, unsigned short word, const PenaltyRow& p) {
+#pragma clang fp contract(off)
+  const unsigned int c = word & 0x7fffu;
+  if (word) l = l > 0.f ? l / p.r : l * p.r;
+  l = l - p.freq * (float)c;
+  l = l - p.pres * (c ? 1.0f : 0.0f);
+  return l;
+}
+
 // Per-row RNG keying: rows with a user seed (req_seeds[b] != 0) draw from
 // (request_seed, output_position) — REPRODUCIBLE for a given request
 // regardless of batch placement or engine step. Unseeded rows draw from
@@ -75,7 +113,14 @@ DEVINL float logit_value(T raw, float softcap, float inv_cap) {
 // ascend (head < vectors < tail), the RNG is keyed on the element index, and
 // ties go to the lower index, so the token does not depend on alignment or
 // on the split.
-template <typename T>
+//
+// PEN = false is the kernel for a batch without penalties. With PEN = true a
+// row whose slot is >= 0 reads its counts alongside the logits, in the same
+// head / vector / tail pieces (each count loaded once): 16-byte (8-byte for
+// fp32 logits) count loads when the count row is aligned like the logits,
+// scalar loads otherwise. A workgroup is one row, so the branch is uniform,
+// and a row with slot -1 runs the plain loops with no table traffic.
+template <typename T, bool PEN>
 __global__ __launch_bounds__(256) void sample_argmax_kernel(
     unsigned long long* __restrict__ out_keys,  // [B], pre-zeroed
     const T* __restrict__ logits,               // [B, V], row stride `stride`
@@ -84,7 +129,11 @@ __global__ __launch_bounds__(256) void sample_argmax_kernel(
     const unsigned int* __restrict__ req_pos,   // [B] output position
     const float* __restrict__ bounds,           // [B] top-k/p keep-bound or null
     int V, long stride, int chunk, float softcap, float inv_cap,
-    unsigned int seed, unsigned int step) {
+    unsigned int seed, unsigned int step,
+    const unsigned short* __restrict__ pen_table,  // [nslots, vpad] or null
+    const int* __restrict__ pen_slots,             // [B], -1 = none
+    const float* __restrict__ pen_params,          // [B, 3] (r, freq, pres)
+    int nslots, long vpad) {
   constexpr int VE = Vec8<T>::kElems;
   const int b = blockIdx.x;
   const int v0 = blockIdx.y * chunk;
@@ -104,8 +153,7 @@ __global__ __launch_bounds__(256) void sample_argmax_kernel(
 
   float best = -3e38f;
   int best_i = v0;
-  auto consider = [&](int v, T raw) {
-    const float l = logit_value(raw, softcap, inv_cap);
+  auto consider_l = [&](int v, float l) {
     if (l < bound) return;
     float x = l * inv_t;
     if (!greedy) {
@@ -114,17 +162,55 @@ __global__ __launch_bounds__(256) void sample_argmax_kernel(
     }
     if (x > best) { best = x; best_i = v; }
   };
+  auto consider = [&](int v, T raw) {
+    consider_l(v, logit_value(raw, softcap, inv_cap));
+  };
   // elements before the first 16-byte boundary at or after row + v0
   const int mis = (int)(((unsigned long)(row + v0) / sizeof(T)) % VE);
   const int vb = min(v1, v0 + (mis ? VE - mis : 0));
   const int ve = vb + (v1 - vb) / VE * VE;
-  if (v0 + (int)threadIdx.x < vb) consider(v0 + threadIdx.x, row[v0 + threadIdx.x]);
-  for (int v = vb + threadIdx.x * VE; v < ve; v += 256 * VE) {
-    const Vec8<T> vec = load16(row + v);
+  PenaltyRow pen{nullptr, 1.0f, 0.0f, 0.0f};
+  if constexpr (PEN)
+    pen = penalty_row(pen_table, pen_slots, pen_params, nslots, vpad, b);
+  if (PEN && pen.cnt) {
+    const unsigned short* cnt = pen.cnt;
+    auto consider_p = [&](int v, T raw, unsigned short word) {
+      consider_l(v, penalize(logit_value(raw, softcap, inv_cap), word, pen));
+    };
+    if (v0 + (int)threadIdx.x < vb)
+      consider_p(v0 + threadIdx.x, row[v0 + threadIdx.x], cnt[v0 + threadIdx.x]);
+    if ((unsigned long)(cnt + vb) % (VE * sizeof(unsigned short)) == 0) {
+      for (int v = vb + threadIdx.x * VE; v < ve; v += 256 * VE) {
+        const Vec8<T> vec = load16(row + v);
+        unsigned short words[VE];
+        if constexpr (VE == 8)
+          *reinterpret_cast<int4*>(words) = *reinterpret_cast<const int4*>(cnt + v);
+        else
+          *reinterpret_cast<int2*>(words) = *reinterpret_cast<const int2*>(cnt + v);
 #pragma unroll
-    for (int j = 0; j < VE; ++j) consider(v + j, vec.data[j]);
+        for (int j = 0; j < VE; ++j) consider_p(v + j, vec.data[j], words[j]);
+      }
+    } else {
+      for (int v = vb + threadIdx.x * VE; v < ve; v += 256 * VE) {
+        const Vec8<T> vec = load16(row + v);
+        unsigned short words[VE];
+#pragma unroll
+        for (int j = 0; j < VE; ++j) words[j] = cnt[v + j];
+#pragma unroll
+        for (int j = 0; j < VE; ++j) consider_p(v + j, vec.data[j], words[j]);
+      }
+    }
+    if (ve + (int)threadIdx.x < v1)
+      consider_p(ve + threadIdx.x, row[ve + threadIdx.x], cnt[ve + threadIdx.x]);
+  } else {
+    if (v0 + (int)threadIdx.x < vb) consider(v0 + threadIdx.x, row[v0 + threadIdx.x]);
+    for (int v = vb + threadIdx.x * VE; v < ve; v += 256 * VE) {
+      const Vec8<T> vec = load16(row + v);
+#pragma unroll
+      for (int j = 0; j < VE; ++j) consider(v + j, vec.data[j]);
+    }
+    if (ve + (int)threadIdx.x < v1) consider(ve + threadIdx.x, row[ve + threadIdx.x]);
   }
-  if (ve + (int)threadIdx.x < v1) consider(ve + threadIdx.x, row[ve + threadIdx.x]);
   // wave reduce (value, index)
   for (int off = WAVE / 2; off > 0; off >>= 1) {
     const float ov = __shfl_xor(best, off, WAVE);
@@ -164,14 +250,25 @@ __global__ __launch_bounds__(256) void sample_argmax_kernel(
 #define TH_TPB 256
 #define TH_XMIN -32.0f
 
-template <typename T>
+// EXT = false is the kernel for a batch with neither min_p nor penalties.
+// With EXT = true a penalised row (slot >= 0) bounds the penalised logits,
+// reading each count next to its logit in every pass, and min_p adds the
+// bound m + T * ln(min_p) ("probability >= min_p x the most likely token's"):
+// the row keeps the intersection, i.e. the larger bound, and a row with
+// min_p alone is done after pass 1, which already has the row max m.
+template <typename T, bool EXT>
 __global__ __launch_bounds__(TH_TPB) void topk_topp_bound_kernel(
     float* __restrict__ out_bound,     // [B] keep-bound on logit_value()
     const T* __restrict__ logits,      // [B, V] as stored
     const float* __restrict__ temps,   // [B]
     const float* __restrict__ top_ps,  // [B]
     const long* __restrict__ top_ks,   // [B] (0 = off)
-    int V, long stride, float softcap, float inv_cap) {
+    int V, long stride, float softcap, float inv_cap,
+    const float* __restrict__ min_ps,              // [B] (0 = off) or null
+    const unsigned short* __restrict__ pen_table,  // [nslots, vpad] or null
+    const int* __restrict__ pen_slots,             // [B], -1 = none
+    const float* __restrict__ pen_params,          // [B, 3] (r, freq, pres)
+    int nslots, long vpad) {
   const int b = blockIdx.x;
   const int tid = threadIdx.x;
   const float T0 = temps[b];
@@ -179,13 +276,33 @@ __global__ __launch_bounds__(TH_TPB) void topk_topp_bound_kernel(
   const long k_lim = top_ks[b];
   const bool need_p = p_lim < 1.0f;
   const bool need_k = k_lim > 0 && k_lim < V;
-  if (T0 <= 0.f || !(need_p || need_k)) {
+  float min_p = 0.f;
+  if constexpr (EXT) min_p = min_ps ? min_ps[b] : 0.f;
+  const bool need_m = EXT && min_p > 0.f;
+  if (T0 <= 0.f || !(need_p || need_k || need_m)) {
     // greedy rows take argmax regardless; unconstrained rows keep all
     if (tid == 0) out_bound[b] = -3e38f;
     return;
   }
   const float inv_t = 1.0f / T0;
   const T* row = logits + (long)b * stride;
+  PenaltyRow pen{nullptr, 1.0f, 0.0f, 0.0f};
+  if constexpr (EXT)
+    pen = penalty_row(pen_table, pen_slots, pen_params, nslots, vpad, b);
+  // The streaming loops exist twice, for rows with and without a count row
+  // (the choice is uniform per workgroup): the penalised one issues the
+  // count load next to the logit load instead of behind a branch that waits
+  // for the logit, the plain one is the loop as it was.
+  const bool penalised = EXT && pen.cnt;
+  auto value = [&](auto with_counts, int v) {
+    const T raw = row[v];
+    if constexpr (decltype(with_counts)::value) {
+      const unsigned short word = pen.cnt[v];
+      return penalize(logit_value(raw, softcap, inv_cap), word, pen);
+    } else {
+      return logit_value(raw, softcap, inv_cap);
+    }
+  };
 
   __shared__ float h_sum[TH_NBINS];
   __shared__ int h_cnt[TH_NBINS];
@@ -194,8 +311,12 @@ __global__ __launch_bounds__(TH_TPB) void topk_topp_bound_kernel(
 
   // ---- pass 1: row max
   float m = -3e38f;
-  for (int v = tid; v < V; v += TH_TPB)
-    m = fmaxf(m, logit_value(row[v], softcap, inv_cap));
+  auto row_max = [&](auto with_counts) {
+    for (int v = tid; v < V; v += TH_TPB)
+      m = fmaxf(m, value(with_counts, v));
+  };
+  if (penalised) row_max(std::true_type{});
+  else row_max(std::false_type{});
   for (int off = WAVE / 2; off > 0; off >>= 1)
     m = fmaxf(m, __shfl_xor(m, off, WAVE));
   if ((tid & (WAVE - 1)) == 0) red[tid / WAVE] = m;
@@ -206,6 +327,19 @@ __global__ __launch_bounds__(TH_TPB) void topk_topp_bound_kernel(
   }
   __syncthreads();
   m = red[0];
+
+  // min_p bound in logit space; logf (not __logf): the bound is compared
+  // with the fp32 torch expression to a few ulp
+  float min_p_bound = -3e38f;
+  if (need_m) {
+#pragma clang fp contract(off)
+    const float t_ln = T0 * logf(min_p);
+    min_p_bound = m + t_ln;
+  }
+  if (EXT && !(need_p || need_k)) {
+    if (tid == 0) out_bound[b] = min_p_bound;
+    return;
+  }
 
   // Histogram window [xlo, xhi) in x-space; elements >= keep_above are
   // already-kept (counted in p_above), elements < xlo already-dropped.
@@ -226,15 +360,19 @@ __global__ __launch_bounds__(TH_TPB) void topk_topp_bound_kernel(
     const float w = (xhi - xlo) / TH_NBINS;
     const float inv_w = 1.0f / w;
     float tail = 0.f;  // mass below xlo (iter 0 only; used for Z)
-    for (int v = tid; v < V; v += TH_TPB) {
-      const float x = (logit_value(row[v], softcap, inv_cap) - m) * inv_t;
-      if (x >= keep_above) continue;   // already kept (counted in p_above)
-      if (x < xlo) { if (iter == 0) tail += __expf(fmaxf(x, -80.f)); continue; }
-      int bin = (int)((x - xlo) * inv_w);
-      bin = bin < 0 ? 0 : (bin >= TH_NBINS ? TH_NBINS - 1 : bin);
-      atomicAdd(&h_sum[bin], __expf(x));
-      atomicAdd(&h_cnt[bin], 1);
-    }
+    auto histogram = [&](auto with_counts) {
+      for (int v = tid; v < V; v += TH_TPB) {
+        const float x = (value(with_counts, v) - m) * inv_t;
+        if (x >= keep_above) continue;   // already kept (counted in p_above)
+        if (x < xlo) { if (iter == 0) tail += __expf(fmaxf(x, -80.f)); continue; }
+        int bin = (int)((x - xlo) * inv_w);
+        bin = bin < 0 ? 0 : (bin >= TH_NBINS ? TH_NBINS - 1 : bin);
+        atomicAdd(&h_sum[bin], __expf(x));
+        atomicAdd(&h_cnt[bin], 1);
+      }
+    };
+    if (penalised) histogram(std::true_type{});
+    else histogram(std::false_type{});
     // reduce tail mass (iter 0: completes Z)
     for (int off = WAVE / 2; off > 0; off >>= 1) tail += __shfl_xor(tail, off, WAVE);
     if ((tid & (WAVE - 1)) == 0) red[tid / WAVE] = tail;
@@ -296,8 +434,28 @@ __global__ __launch_bounds__(TH_TPB) void topk_topp_bound_kernel(
     }
     __syncthreads();
   }
-  if (tid == 0)
-    out_bound[b] = (bound_x <= -3e37f) ? -3e38f : (m + bound_x * T0);
+  if (tid == 0) {
+    const float kp_bound = (bound_x <= -3e37f) ? -3e38f : (m + bound_x * T0);
+    out_bound[b] = EXT ? fmaxf(kp_bound, min_p_bound) : kp_bound;
+  }
+}
+
+// After a sampling call: one thread per row adds the sampled token to the
+// row's count (bits 0-14, saturating; bit 15 kept). Slots are distinct per
+// row, so plain loads and stores suffice.
+__global__ void penalty_count_tokens_kernel(
+    unsigned short* __restrict__ table,  // [nslots, vpad]
+    const int* __restrict__ slots,       // [B], -1 = none
+    const long* __restrict__ tokens,     // [B]
+    int B, int nslots, long vpad) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  const int slot = slots[b];
+  const long tok = tokens[b];
+  if (slot < 0 || slot >= nslots || tok < 0 || tok >= vpad) return;
+  unsigned short* p = table + (long)slot * vpad + tok;
+  const unsigned short word = *p;
+  if ((word & 0x7fffu) != 0x7fffu) *p = (unsigned short)(word + 1);
 }
 
 __global__ void unpack_keys_kernel(long* __restrict__ out,

@@ -286,14 +286,45 @@ def varlen_prefill_attention(
     return out
 
 
+def _per_row(x, like: torch.Tensor) -> torch.Tensor:
+    """A float or a [B] tensor as an fp32 [B, 1] column on `like`'s device."""
+    t = torch.as_tensor(x, dtype=torch.float32, device=like.device)
+    return t.reshape(-1, 1).expand(like.size(0), 1)
+
+
+def apply_penalties(
+    logits: torch.Tensor,     # [B, vocab] fp32, soft-cap already applied
+    counts: torch.Tensor,     # [B, vocab] int: occurrences in the output so far
+    in_prompt: torch.Tensor,  # [B, vocab] bool: token occurs in the prompt
+    r,                        # repetition penalty, float or [B]
+    freq,                     # frequency penalty, float or [B]
+    pres,                     # presence penalty, float or [B]
+) -> torch.Tensor:
+    """Repetition, frequency and presence penalties, in this order. r, freq
+    and pres are held as fp32 tensors, so `l / r` is a true fp32 division
+    (torch turns a division by a Python scalar into a multiply by its
+    reciprocal); the HIP sampler computes the same expression bit for bit."""
+    l = logits.float()
+    r, freq, pres = _per_row(r, l), _per_row(freq, l), _per_row(pres, l)
+    seen = in_prompt | (counts > 0)
+    l = torch.where(seen, torch.where(l > 0, l / r, l * r), l)
+    l = l - freq * counts.float()
+    l = l - pres * (counts > 0).float()
+    return l
+
+
 def sample_tokens(
     logits: torch.Tensor,  # [B, vocab] float
     temperatures: torch.Tensor,  # [B]
     top_ps: torch.Tensor,  # [B]
     top_ks: torch.Tensor,  # [B] int (0 = off)
     generator: Optional[torch.Generator] = None,
+    min_p: Optional[torch.Tensor] = None,  # [B] (0 = off)
 ) -> torch.Tensor:
-    """Temperature / top-k / top-p sampling; greedy where temperature == 0."""
+    """Temperature / top-k / top-p / min_p sampling; greedy where temperature
+    == 0. min_p keeps {v : l[v] >= max l + T * ln(min_p)} of the unscaled
+    logits l, i.e. probability >= min_p x the most likely token's, and is
+    intersected with the top-k/top-p keep set."""
     B, V = logits.shape
     out = torch.empty(B, dtype=torch.long, device=logits.device)
     greedy_mask = temperatures <= 0
@@ -302,6 +333,11 @@ def sample_tokens(
     sample_idx = (~greedy_mask).nonzero(as_tuple=True)[0]
     for i in sample_idx.tolist():
         l = logits[i].float() / float(temperatures[i])
+        drop = None
+        if min_p is not None and float(min_p[i]) > 0:
+            raw = logits[i].float()
+            bound = raw.max() + temperatures[i].float() * torch.log(min_p[i].float())
+            drop = raw < bound
         k = int(top_ks[i])
         if k > 0 and k < V:
             kth = torch.topk(l, k).values[-1]
@@ -314,6 +350,8 @@ def sample_tokens(
             cut = (cum - probs) >= p  # keep tokens whose preceding mass < p
             sorted_l[cut] = float("-inf")
             l = torch.full_like(l, float("-inf")).scatter(0, sorted_i, sorted_l)
+        if drop is not None:
+            l = l.masked_fill(drop, float("-inf"))
         probs = torch.softmax(l, dim=-1)
         out[i] = torch.multinomial(probs, 1, generator=generator).squeeze(0)
     return out

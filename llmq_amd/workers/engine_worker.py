@@ -430,6 +430,13 @@ class EngineWorker(BaseWorker):
             max_tokens=int(pick(job.max_tokens, "max_tokens", self.config.max_tokens)),
             stop=list(stop) if stop else None,
             seed=job.seed,
+            repetition_penalty=float(
+                pick(job.repetition_penalty, "repetition_penalty", 1.0)),
+            presence_penalty=float(
+                pick(job.presence_penalty, "presence_penalty", 0.0)),
+            frequency_penalty=float(
+                pick(job.frequency_penalty, "frequency_penalty", 0.0)),
+            min_p=float(pick(job.min_p, "min_p", 0.0)),
         )
 
     def _format_prompt(self, job: Job) -> str:
