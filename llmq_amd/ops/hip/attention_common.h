@@ -164,20 +164,40 @@ DEVINL void attn_pv_tile(const short* img, const short* p_tile,
 // discipline for these, per guide §5.7 (its LDS-DMA recipe: M0 carries the
 // wave-uniform LDS byte address, saved/written/restored in ONE statement;
 // the s_nop is the SALU-write→M0-read wait state).
+//
+// NT selects the cache policy of the load, one asm statement per policy:
+// false = default (the line allocates in L2 and the Infinity Cache: tiles
+// that other workgroups re-read, i.e. prefill K/V and GEMM operands), true =
+// `nt` (non-temporal: a once-read stream, i.e. the decode K/V cache, does not
+// evict what the neighbouring kernels re-read). The policy cannot change a
+// loaded value.
+template <bool NT = false>
 DEVINL void glds16(const void* src, void* lds_dst_uniform) {
   unsigned lds_off = (unsigned)(unsigned long)(
       (__attribute__((address_space(3))) char*)lds_dst_uniform);
   lds_off = __builtin_amdgcn_readfirstlane(lds_off);
   unsigned keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\t"
-      "s_mov_b32 m0, %2\n\t"
-      "s_nop 0\n\t"
-      "global_load_lds_dwordx4 %1, off\n\t"
-      "s_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(src), "s"(lds_off)
-      : "memory");
+  if constexpr (NT) {
+    asm volatile(
+        "s_mov_b32 %0, m0\n\t"
+        "s_mov_b32 m0, %2\n\t"
+        "s_nop 0\n\t"
+        "global_load_lds_dwordx4 %1, off nt\n\t"
+        "s_mov_b32 m0, %0"
+        : "=&s"(keep)
+        : "v"(src), "s"(lds_off)
+        : "memory");
+  } else {
+    asm volatile(
+        "s_mov_b32 %0, m0\n\t"
+        "s_mov_b32 m0, %2\n\t"
+        "s_nop 0\n\t"
+        "global_load_lds_dwordx4 %1, off\n\t"
+        "s_mov_b32 m0, %0"
+        : "=&s"(keep)
+        : "v"(src), "s"(lds_off)
+        : "memory");
+  }
 }
 
 DEVINL void pipe_barrier() {  // lgkm drain + raw barrier (glds may span)

@@ -210,8 +210,49 @@ void rope_and_cache(at::Tensor q, at::Tensor k, at::Tensor value,
   const int bs = k_cache.size(2);
   TORCH_CHECK(q.stride(1) == d && k.stride(1) == d, "head dim must be packed");
   const bool fp8_cache = k_cache.scalar_type() == at::kFloat8_e4m3fn;
+  // Vector path: the fused QK-norm kernel's mapping with the norm compiled
+  // out (16-lane group per head, 16-byte accesses, no per-element divide),
+  // bit-identical to rope_and_cache_kernel. It covers 2-byte T at head dims
+  // 64/128/256 when every address it forms is aligned for its pieces (see
+  // qknorm_rope_and_cache); everything else keeps the scalar kernel.
+  // LLMQ_ROPE_VEC=0 selects the scalar kernel everywhere (A/B and the
+  // bitwise-equality test). Read per call, like LLMQ_DECODE_PIPE.
+  const char* ve = getenv("LLMQ_ROPE_VEC");
+  bool vec = !(ve && atoi(ve) == 0) && q.element_size() == 2 &&
+             (d == 64 || d == 128 || d == 256);
+  if (vec) {
+    const long piece = std::min<long>(16, (d / 32) * 2);
+    auto aligned = [&](const at::Tensor& t, long row_stride, long align) {
+      return reinterpret_cast<uintptr_t>(t.data_ptr()) % align == 0 &&
+             (row_stride * t.element_size()) % align == 0;
+    };
+    vec = value.dim() == 3 && value.stride(2) == 1 && value.stride(1) == d &&
+          cos_sin.is_contiguous() && cos_sin.size(-1) == d &&
+          k_cache.is_contiguous() && v_cache.is_contiguous() &&
+          aligned(q, q.stride(0), piece) && aligned(k, k.stride(0), piece) &&
+          aligned(value, value.stride(0), 16) && aligned(k_cache, 0, 16) &&
+          aligned(v_cache, 0, 16) && aligned(cos_sin, 0, 16);
+  }
   dispatch_dtype(q, "rope_and_cache", [&]<typename T>() {
     dispatch_cache_type<T>(fp8_cache, [&]<typename TC>() {
+      if constexpr (sizeof(T) == 2) {
+        if (vec) {
+          dispatch_head_dim<64, 128, 256>(d, [&]<int HD>() {
+            hipLaunchKernelGGL(
+                (qknorm_rope_and_cache_kernel<T, TC, HD, false>), dim3(T_),
+                dim3(256), 0, stream(), reinterpret_cast<T*>(q.data_ptr()),
+                reinterpret_cast<T*>(k.data_ptr()),
+                reinterpret_cast<const T*>(value.data_ptr()),
+                reinterpret_cast<TC*>(k_cache.data_ptr()),
+                reinterpret_cast<TC*>(v_cache.data_ptr()),
+                (const T*)nullptr, (const T*)nullptr, 0.f, 0.f,
+                positions.data_ptr<long>(), cos_sin.data_ptr<float>(),
+                slot_mapping.data_ptr<long>(), hq, hk, bs, q.stride(0),
+                k.stride(0), value.stride(0));
+          });
+          return;
+        }
+      }
       hipLaunchKernelGGL((rope_and_cache_kernel<T, TC>), dim3(T_), dim3(256), 0,
                          stream(), reinterpret_cast<T*>(q.data_ptr()),
                          reinterpret_cast<T*>(k.data_ptr()),
@@ -453,6 +494,17 @@ void launch_decode(at::Tensor& out, const at::Tensor& q, const at::Tensor& kc,
       const char* pe = getenv("LLMQ_DECODE_PIPE");
       const int pipe_kt = pe ? atoi(pe) : 64;
       const bool pipe = pipe_kt > 0 && max_blocks <= PD_MAX_BT;
+      // Cache policy of the pipe kernels' K/V stream: `nt` (default) on
+      // the DMAs that consume whole lines (bf16: K; fp8: K and raw V)
+      // streams the once-read cache past L2 and the Infinity Cache;
+      // LLMQ_DECODE_KV_NT=0 selects the default-policy instantiation (A/B
+      // runs and the equality test). Read per call, like LLMQ_DECODE_PIPE.
+      const char* nte = getenv("LLMQ_DECODE_KV_NT");
+      const bool kv_nt = !(nte && atoi(nte) == 0);
+      auto dispatch_kv_nt = [&](auto&& f) {
+        if (kv_nt) f.template operator()<true>();
+        else f.template operator()<false>();
+      };
       // NREG: how many of a lane's 4 softmax registers hold q-heads with
       // the kernels' row placement (heads 4*reg .. 4*reg+3 in register reg):
       // ceil(G/4), with 3 rounded up to 4.
@@ -463,14 +515,20 @@ void launch_decode(at::Tensor& out, const at::Tensor& q, const at::Tensor& kc,
       };
       dispatch_head_dim<128, 256>(D, [&]<int HD>() {
         dispatch_nreg([&]<int NREG>() {
-          if (fp8_cache) {
+          if (fp8_cache && pipe) {
+            dispatch_kv_nt([&]<bool NT>() {
+              launch.template operator()<HD, F8>(
+                  paged_decode_pipe_fp8_kernel<HD, 8, NREG, NT>);
+            });
+          } else if (fp8_cache) {
             launch.template operator()<HD, F8>(
-                pipe ? paged_decode_pipe_fp8_kernel<HD, 8, NREG>
-                     : paged_decode_mfma_kernel<HD, 8, NREG, F8>);
+                paged_decode_mfma_kernel<HD, 8, NREG, F8>);
           } else if (pipe) {
-            launch.template operator()<HD, BF>(
-                pipe_kt >= 128 ? paged_decode_pipe_kernel<HD, 8, 128, NREG>
-                               : paged_decode_pipe_kernel<HD, 8, 64, NREG>);
+            dispatch_kv_nt([&]<bool NT>() {
+              launch.template operator()<HD, BF>(
+                  pipe_kt >= 128 ? paged_decode_pipe_kernel<HD, 8, 128, NREG, NT>
+                                 : paged_decode_pipe_kernel<HD, 8, 64, NREG, NT>);
+            });
           } else {
             launch.template operator()<HD, BF>(
                 paged_decode_mfma_kernel<HD, 8, NREG, BF>);

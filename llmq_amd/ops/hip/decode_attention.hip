@@ -637,7 +637,16 @@ __global__ __launch_bounds__(NW * WAVE) void paged_decode_mfma_kernel(
 // occupancy below that (the r1 lesson: this kernel is governed by
 // waves/SIMD, every latency trick that cost occupancy lost). The 128-key
 // chunk is 1 workgroup/CU by LDS (2 waves/SIMD) — let it use 196.
-template <int HEAD_DIM, int NW, int PD_KT, int NREG>
+// KV_NT: cache policy of the K DMAs (glds16<KV_NT>). The decode K/V stream
+// is read once per step, so the default instantiation streams K `nt` past L2
+// and the Infinity Cache: a K DMA consumes whole 128-byte lines (two 512-byte
+// key rows per instruction). The V DMAs keep the default policy: one of them
+// takes 32 bytes from each of 32 rows (a tr16 subtile), and the line's other
+// 96 bytes are the same wave's next three DMAs, which must hit the line in
+// L2; with `nt` on V the kernel measured 0.468 against 0.369 ms
+// (profiles/decode_kv_stream.md). Block-table loads, q loads and stores keep
+// the default policy too.
+template <int HEAD_DIM, int NW, int PD_KT, int NREG, bool KV_NT>
 __global__ __launch_bounds__(NW * WAVE, (PD_KT <= 64 ? 4 : 2)) void paged_decode_pipe_kernel(
     __hip_bfloat16* __restrict__ out,      // [B, H, D]
     const __hip_bfloat16* __restrict__ q,  // [B, H, D]
@@ -769,7 +778,7 @@ __global__ __launch_bounds__(NW * WAVE, (PD_KT <= 64 ? 4 : 2)) void paged_decode
 #pragma unroll
     for (int j = 0; j < NI_K; ++j) {
       const int off = __builtin_amdgcn_readfirstlane((wid * NI_K + j) * 512);
-      glds16(src[j], dst + off);
+      glds16<KV_NT>(src[j], dst + off);
     }
   };
   // A wave's NI_V subtiles are consecutive 16-dim tiles of ONE 32-key group,
@@ -783,7 +792,7 @@ __global__ __launch_bounds__(NW * WAVE, (PD_KT <= 64 ? 4 : 2)) void paged_decode
     for (int j = 0; j < NI_V; ++j) {
       const int off =
           __builtin_amdgcn_readfirstlane((wid * NI_V + j) * V_SUB_STRIDE);
-      glds16(row + j * 16, dst + off);
+      glds16(row + j * 16, dst + off);  // default policy: see KV_NT
     }
   };
   // ---- prologue: block table visible, then K(first) in flight
@@ -862,8 +871,10 @@ __global__ __launch_bounds__(NW * WAVE, (PD_KT <= 64 ? 4 : 2)) void paged_decode
 // Y-back is free during i (its image is only rebuilt by i+1's convert);
 // Y-front K(i+1) and Y-back V(i)raw are disjoint ranges. LDS stays at
 // 2 × image + p + bt ≈ 74 KB -> 2 workgroups/CU, same as the bf16 pipe.
+// KV_NT: both DMAs (fp8 K rows and the linear raw V) consume whole lines, so
+// both stream `nt`.
 
-template <int HEAD_DIM, int NW, int NREG>
+template <int HEAD_DIM, int NW, int NREG, bool KV_NT>
 __global__ __launch_bounds__(NW * WAVE, 4) void paged_decode_pipe_fp8_kernel(
     __hip_bfloat16* __restrict__ out,      // [B, H, D]
     const __hip_bfloat16* __restrict__ q,  // [B, H, D]
@@ -979,7 +990,7 @@ __global__ __launch_bounds__(NW * WAVE, 4) void paged_decode_pipe_fp8_kernel(
 #pragma unroll
     for (int j = 0; j < NI_K; ++j) {
       const int off = __builtin_amdgcn_readfirstlane((wid * NI_K + j) * 512);
-      glds16(src[j], reinterpret_cast<char*>(dst) + off * 2);
+      glds16<KV_NT>(src[j], reinterpret_cast<char*>(dst) + off * 2);
     }
   };
   // V raw fp8, linear [PD_KT][D] bytes into the back half of `dst`
@@ -996,7 +1007,7 @@ __global__ __launch_bounds__(NW * WAVE, 4) void paged_decode_pipe_fp8_kernel(
 #pragma unroll
     for (int j = 0; j < NI_VR; ++j) {
       const int off = __builtin_amdgcn_readfirstlane((wid * NI_VR + j) * 1024);
-      glds16(src[j], back + off);
+      glds16<KV_NT>(src[j], back + off);
     }
   };
 

@@ -141,6 +141,13 @@ __global__ void rope_and_cache_kernel(
 // Rounding: the normed value stays fp32 into the rotation; the only rounding
 // to T is at the store. An fp8 cache gets the quantization of that T-rounded
 // k, exactly as rope_and_cache_kernel writes it.
+//
+// NORM == false drops the norm (no weight loads, no sum of squares, no
+// shuffle reduction, no `inv`; q_weight/k_weight/eps/offset are unused and
+// the weights may be null): the same mapping then does rope_and_cache_kernel's
+// job with 16-byte accesses and no per-element divide. The rotation is
+// written with that kernel's compiled fma order, so all four outputs are
+// bit-identical to it (tests/test_rope_cache_vec.py).
 
 template <int BYTES> struct RawBytes;
 template <> struct RawBytes<2> { using type = unsigned short; };
@@ -170,7 +177,7 @@ struct Frag {
   }
 };
 
-template <typename T, typename TC, int D>
+template <typename T, typename TC, int D, bool NORM = true>
 __global__ __launch_bounds__(256) void qknorm_rope_and_cache_kernel(
     T* __restrict__ q,             // [T, Hq, D] (row stride q_stride)
     T* __restrict__ k,             // [T, Hk, D]
@@ -207,29 +214,46 @@ __global__ __launch_bounds__(256) void qknorm_rope_and_cache_kernel(
     const int kh = h - num_q_heads;
     T* base = is_q ? q + (long)token * q_stride + (long)h * D
                    : k + (long)token * k_stride + (long)kh * D;
-    const T* w = is_q ? q_weight : k_weight;
-    Frag<T, E> lo, hi, wlo, whi;
+    Frag<T, E> lo, hi;
     lo.load(base + d0);
     hi.load(base + HALF + d0);
-    wlo.load(w + d0);
-    whi.load(w + HALF + d0);
+    if constexpr (NORM) {
+      const T* w = is_q ? q_weight : k_weight;
+      Frag<T, E> wlo, whi;
+      wlo.load(w + d0);
+      whi.load(w + HALF + d0);
 
-    float x1[E], x2[E];
-    float ss = 0.f;
+      float x1[E], x2[E];
+      float ss = 0.f;
 #pragma unroll
-    for (int j = 0; j < E; ++j) {
-      x1[j] = to_f32(lo.data[j]);
-      x2[j] = to_f32(hi.data[j]);
-      ss += x1[j] * x1[j] + x2[j] * x2[j];
-    }
-    ss = group_reduce_sum<GROUP>(ss);
-    const float inv = rsqrtf(ss / D + eps);
+      for (int j = 0; j < E; ++j) {
+        x1[j] = to_f32(lo.data[j]);
+        x2[j] = to_f32(hi.data[j]);
+        ss += x1[j] * x1[j] + x2[j] * x2[j];
+      }
+      ss = group_reduce_sum<GROUP>(ss);
+      const float inv = rsqrtf(ss / D + eps);
 #pragma unroll
-    for (int j = 0; j < E; ++j) {
-      const float y1 = x1[j] * inv * (to_f32(wlo.data[j]) + offset);
-      const float y2 = x2[j] * inv * (to_f32(whi.data[j]) + offset);
-      lo.data[j] = from_f32<T>(y1 * c.data[j] - y2 * s.data[j]);
-      hi.data[j] = from_f32<T>(y2 * c.data[j] + y1 * s.data[j]);
+      for (int j = 0; j < E; ++j) {
+        const float y1 = x1[j] * inv * (to_f32(wlo.data[j]) + offset);
+        const float y2 = x2[j] * inv * (to_f32(whi.data[j]) + offset);
+        lo.data[j] = from_f32<T>(y1 * c.data[j] - y2 * s.data[j]);
+        hi.data[j] = from_f32<T>(y2 * c.data[j] + y1 * s.data[j]);
+      }
+    } else {
+#pragma unroll
+      for (int j = 0; j < E; ++j) {
+        const float x1 = to_f32(lo.data[j]);
+        const float x2 = to_f32(hi.data[j]);
+        // rope_and_cache_kernel's `x1 * c - x2 * s` and `x2 * c + x1 * s`
+        // compile to one rounded product and one fma each: x2*s and x2*c are
+        // the rounded products (its ISA; confirmed on the GPU, where the
+        // other choice for the high half differs in about 1 element in
+        // 10^5). Spelled out, because left to contraction this body rounds
+        // x1*s instead.
+        lo.data[j] = from_f32<T>(fmaf(x1, c.data[j], -(x2 * s.data[j])));
+        hi.data[j] = from_f32<T>(fmaf(x1, s.data[j], x2 * c.data[j]));
+      }
     }
     lo.store(base + d0);
     hi.store(base + HALF + d0);
