@@ -1,6 +1,7 @@
 // Shared device helpers for the attention kernels (prefill + decode): MFMA
 // fragment vector types, the K swizzle and its S slab, the V tr16 subtile
-// image (index maps, A-fragment read, PV tile), the hidden-from-hipcc
+// image (index maps, A-fragment read, PV tile) and the bf16 pipe decode
+// kernel's V line image (the same, cut along cache lines), the hidden-from-hipcc
 // global->LDS DMA with its hand-counted barriers, and the packed fp8
 // converter. Helpers are forced inline, take registers by reference and LDS
 // as pointers into the CALLER's storage: none declares a __shared__ object
@@ -149,6 +150,217 @@ DEVINL void attn_pv_tile(const short* img, const short* p_tile,
 #pragma unroll
     for (int ks = 0; ks < KT / 32; ++ks) {
       const bf16x8_t a = v_img_afrag(img, ks * (D / 16) + dtile0 + dt, lane);
+      const bf16x8_t b = *reinterpret_cast<const bf16x8_t*>(
+          &p_tile[col * KT + ks * 32 + kgrp * 8]);
+      ot[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, ot[dt], 0, 0, 0);
+    }
+  }
+}
+
+// ---- V "line image" (bf16 pipe decode kernel only) --
+// The subtile image above makes one V DMA take 32 bytes from each of 32 cache
+// rows: every 128-byte line is requested by four instructions, so V cannot
+// stream `nt`. ds_read_b64_tr_b16 takes per-lane addresses, so the image can
+// be cut along cache lines instead: a PIECE is 8 keys × 64 dims = eight whole
+// 128-byte lines, filled by ONE lane-linear 1 KiB DMA. Piece p = (key octet
+// o) * (D/64) + dim/64 sits at element p * 512, unpadded (the image is
+// exactly the K tile's size). Inside a piece, lane = 16-byte slot, with
+// kk = key & 7 and gg = (dim & 63) / 8, in one of two orders:
+//   1: slot = gg * 8 + (kk ^ ((o & 1) << 2))
+//   2: slot = kk * 8 + (gg ^ (2 * ((kk >> 1) & 1)) ^ (4 * (o & 1)))
+// Both make every PV A-fragment read conflict-free under the tr16 bank model
+// (two groups of 32 lanes, bank = (byte address / 4) mod 64): the 32 lanes of
+// a group read four keys of each of two octets o, o+1, two granules and two
+// halves each, and the XORs spread them over 32 distinct 8-byte bank pairs.
+// In order 1 adjacent lanes read different rows, in order 2 one line.
+// D = 256 uses order 2: it measured faster than order 1 wherever the two
+// differ (ragged batch, split-KV, 128-key chunks) and needs fewer VGPRs
+// there (order 1 spills at NREG = 4). D = 128 uses order 1: order 2 costs
+// the NREG = 4 instantiation a wave of occupancy (98 VGPRs against 94) and
+// measured 3.5 % slower there with K-only `nt`.
+// profiles/decode_v_lines.md has both.
+constexpr int v_line_order(int d) { return d >= 256 ? 2 : 1; }
+constexpr int V_PIECE_ELEMS = 512;
+
+constexpr int v_line_npiece(int kt, int d) { return (kt / 8) * (d / 64); }
+constexpr int v_line_elems(int kt, int d) { return v_line_npiece(kt, d) * V_PIECE_ELEMS; }
+
+template <int D>
+constexpr int v_line_slot(int o, int kk, int gg) {
+  if (v_line_order(D) == 1) return gg * 8 + (kk ^ ((o & 1) << 2));
+  return kk * 8 + (gg ^ (2 * ((kk >> 1) & 1)) ^ (4 * (o & 1)));
+}
+
+// Forward map: element (key, d) of the tile, d a multiple of 4 -> image
+// element index.
+template <int D>
+constexpr int v_line_index(int key, int d) {
+  const int o = key >> 3;
+  return (o * (D / 64) + d / 64) * V_PIECE_ELEMS +
+         v_line_slot<D>(o, key & 7, (d & 63) >> 3) * 8 + (d & 7);
+}
+
+// Inverse map: lane `lane` of the DMA that fills piece p (elements
+// p*512 + lane*8 .. +7) must SOURCE this (key, dim). The pieces of one key
+// octet are consecutive, share `key` and step `dim` by 64.
+template <int D>
+constexpr VImgSrc v_line_source(int piece, int lane) {
+  const int o = piece / (D / 64), pj = piece % (D / 64);
+  int kk = 0, gg = 0;
+  if (v_line_order(D) == 1) {
+    gg = lane >> 3;
+    kk = (lane & 7) ^ ((o & 1) << 2);
+  } else {
+    kk = lane >> 3;
+    gg = (lane & 7) ^ (2 * ((kk >> 1) & 1)) ^ (4 * (o & 1));
+  }
+  return {o * 8 + kk, pj * 64 + gg * 8};
+}
+
+// Image element read by `lane` for the PV A-fragment of 16-dim tile `dtile`,
+// 32-key group `ks`, half h (0 = lo, 1 = hi): v_img_afrag's semantics, i.e. 4
+// bf16 of key ks*32 + kgrp*8 + h*4 + i/4 at dims dtile*16 + (i%4)*4, with
+// kgrp = lane/16 and i = lane%16.
+template <int D>
+constexpr int v_line_afrag_elem(int dtile, int ks, int h, int lane) {
+  const int kgrp = lane >> 4, i = lane & 15;
+  return v_line_index<D>(ks * 32 + kgrp * 8 + h * 4 + (i >> 2),
+                         dtile * 16 + (i & 3) * 4);
+}
+
+// The PV reads of a wave that owns DT dim tiles from `dtile0` (a multiple of
+// DT) decompose into NB chunk-invariant per-lane bases plus compile-time
+// offsets: order 1 keeps one base per half h (the XOR flips bit 2 of the
+// slot lane-dependently) and steps dim tiles by a constant; order 2 the
+// reverse.
+template <int D, int DT>
+constexpr int v_line_nbase() { return v_line_order(D) == 1 ? 2 : DT; }
+template <int D>
+constexpr int v_line_rd_base(int dtile0, int b, int lane) {
+  return v_line_order(D) == 1 ? v_line_afrag_elem<D>(dtile0, 0, b, lane)
+                              : v_line_afrag_elem<D>(dtile0 + b, 0, 0, lane);
+}
+template <int D>
+constexpr int v_line_rd_sel(int dt, int h) { return v_line_order(D) == 1 ? h : dt; }
+template <int D>
+constexpr int v_line_rd_off(int dt, int ks, int h) {
+  return ks * (D / 2) * 64 + (v_line_order(D) == 1 ? dt * 128 : h * 256);
+}
+
+// Compile-time proof for one (KT, D) and DT dim tiles per wave:
+//  1. forward and inverse maps are inverses; the DMAs cover every granule of
+//     the tile exactly once;
+//  2. every piece is eight whole 128-byte-aligned line segments, one from
+//     each of the eight rows of ONE key octet, and the next piece of the
+//     octet is the same rows 64 dims on;
+//  3. the A-fragment reads of every (dtile, ks, h) are conflict-free: within
+//     each group of 32 lanes no two lanes touch the same 4-byte bank;
+//  4. every such read is v_line_rd_base + v_line_rd_off.
+// 1-2 are v_line_maps_ok, 3-4 v_line_reads_ok for one 32-key group; each is
+// evaluated as a constant of its own (the constexpr step budget is per
+// constant) and v_line_layout_ok is their conjunction.
+template <int KT, int D>
+constexpr bool v_line_maps_ok() {
+  if (D % 64 || KT % 32) return false;
+  bool seen[KT * D / 8] = {};
+  for (int p = 0; p < v_line_npiece(KT, D); ++p) {
+    unsigned segs[8] = {};
+    const int o = p / (D / 64), pj = p % (D / 64);
+    for (int lane = 0; lane < WAVE; ++lane) {
+      const VImgSrc s = v_line_source<D>(p, lane);
+      if (s.key < 0 || s.key >= KT || s.dim < 0 || s.dim >= D || s.dim % 8) return false;
+      if (v_line_index<D>(s.key, s.dim) != p * V_PIECE_ELEMS + lane * 8) return false;
+      bool& hit = seen[s.key * (D / 8) + s.dim / 8];
+      if (hit) return false;
+      hit = true;
+      // rows of octet o, bytes [128*pj, 128*pj + 128) of the row
+      if (s.key >> 3 != o || s.dim / 64 != pj) return false;
+      segs[s.key & 7] |= 1u << ((s.dim & 63) >> 3);
+      if (pj + 1 < D / 64) {
+        const VImgSrc n = v_line_source<D>(p + 1, lane);
+        if (n.key != s.key || n.dim != s.dim + 64) return false;
+      }
+    }
+    for (unsigned m : segs)
+      if (m != 0xffu) return false;
+  }
+  for (bool hit : seen)
+    if (!hit) return false;
+  return true;
+}
+
+template <int KT, int D, int DT>
+constexpr bool v_line_reads_ok(int ks) {
+  if ((D / 16) % DT || 4 % DT) return false;
+  if (ks >= KT / 32) return true;
+  for (int dtile = 0; dtile < D / 16; ++dtile)
+    for (int h = 0; h < 2; ++h)
+      for (int grp = 0; grp < 2; ++grp) {
+        unsigned long long busy = 0;  // one bit per 4-byte bank
+        for (int l = 0; l < 32; ++l) {
+          const int lane = grp * 32 + l;
+          const int e = v_line_afrag_elem<D>(dtile, ks, h, lane);
+          if (e % 4 || e < 0 || e + 4 > v_line_elems(KT, D)) return false;
+          const int dt = dtile % DT;
+          if (e != v_line_rd_base<D>(dtile - dt, v_line_rd_sel<D>(dt, h), lane) +
+                       v_line_rd_off<D>(dt, ks, h))
+            return false;
+          // an 8-byte read spans two banks
+          const unsigned long long m = 3ull << ((e / 2) % 64);
+          if (busy & m) return false;
+          busy |= m;
+        }
+      }
+  return true;
+}
+
+template <int KT, int D>
+constexpr bool v_line_maps_ok_v = v_line_maps_ok<KT, D>();
+template <int KT, int D, int DT, int KS>
+constexpr bool v_line_reads_ok_v = v_line_reads_ok<KT, D, DT>(KS);
+template <int KT, int D, int DT>
+constexpr bool v_line_layout_ok_v =
+    KT <= 128 && v_line_maps_ok_v<KT, D> && v_line_reads_ok_v<KT, D, DT, 0> &&
+    v_line_reads_ok_v<KT, D, DT, 1> && v_line_reads_ok_v<KT, D, DT, 2> &&
+    v_line_reads_ok_v<KT, D, DT, 3>;
+static_assert(v_line_layout_ok_v<64, 128, 1> && v_line_layout_ok_v<128, 128, 1> &&
+              v_line_layout_ok_v<64, 256, 2> && v_line_layout_ok_v<128, 256, 2>,
+              "V line image: maps disagree, a piece is not eight whole lines, or "
+              "a PV read has a bank conflict");
+
+// PV A-fragment from the line image: the two transpose reads of v_img_afrag
+// at this lane's own element indices.
+DEVINL bf16x8_t v_line_afrag(const short* img, int e_lo, int e_hi) {
+  bf16x4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)&img[e_lo]);
+  bf16x4v hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)&img[e_hi]);
+  bf16x8_t a;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    a[j] = __bfloat16_as_short((__hip_bfloat16)lo[j]);
+    a[4 + j] = __bfloat16_as_short((__hip_bfloat16)hi[j]);
+  }
+  return a;
+}
+
+// attn_pv_tile on the line image: same operands, same MFMA order. `vb` holds
+// the lane's v_line_rd_base values for this wave's dim slab (chunk-invariant).
+template <int D, int KT, int DT>
+DEVINL void attn_pv_tile_lines(const short* img, const int (&vb)[v_line_nbase<D, DT>()],
+                               const short* p_tile, const float* alpha_s,
+                               bool rescale, f32x4_t (&ot)[DT], int lane) {
+  const int col = lane & 15, kgrp = lane >> 4;
+  const float alpha_q = rescale ? alpha_s[col] : 1.f;
+#pragma unroll
+  for (int dt = 0; dt < DT; ++dt) {
+    if (rescale) {
+      ot[dt][0] *= alpha_q; ot[dt][1] *= alpha_q;
+      ot[dt][2] *= alpha_q; ot[dt][3] *= alpha_q;
+    }
+#pragma unroll
+    for (int ks = 0; ks < KT / 32; ++ks) {
+      const bf16x8_t a = v_line_afrag(
+          img, vb[v_line_rd_sel<D>(dt, 0)] + v_line_rd_off<D>(dt, ks, 0),
+          vb[v_line_rd_sel<D>(dt, 1)] + v_line_rd_off<D>(dt, ks, 1));
       const bf16x8_t b = *reinterpret_cast<const bf16x8_t*>(
           &p_tile[col * KT + ks * 32 + kgrp * 8]);
       ot[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, ot[dt], 0, 0, 0);

@@ -495,15 +495,37 @@ void launch_decode(at::Tensor& out, const at::Tensor& q, const at::Tensor& kc,
       const int pipe_kt = pe ? atoi(pe) : 64;
       const bool pipe = pipe_kt > 0 && max_blocks <= PD_MAX_BT;
       // Cache policy of the pipe kernels' K/V stream: `nt` (default) on
-      // the DMAs that consume whole lines (bf16: K; fp8: K and raw V)
-      // streams the once-read cache past L2 and the Infinity Cache;
-      // LLMQ_DECODE_KV_NT=0 selects the default-policy instantiation (A/B
-      // runs and the equality test). Read per call, like LLMQ_DECODE_PIPE.
+      // the DMAs that consume whole lines streams the once-read cache past
+      // L2 and the Infinity Cache. LLMQ_DECODE_KV_NT: 0 = the default-policy
+      // instantiation (A/B runs and the equality tests), 1 = K only (bf16)
+      // / K and raw V (fp8), 2 = also the bf16 V DMAs, which consume whole
+      // lines only in the line image (fp8 and the subtile image: same as 1).
+      // Read per call, like LLMQ_DECODE_PIPE.
+      constexpr int DECODE_KV_NT_DEFAULT = 2;
       const char* nte = getenv("LLMQ_DECODE_KV_NT");
-      const bool kv_nt = !(nte && atoi(nte) == 0);
+      const int kv_nt_env = nte ? atoi(nte) : DECODE_KV_NT_DEFAULT;
+      const bool kv_nt = kv_nt_env != 0;
       auto dispatch_kv_nt = [&](auto&& f) {
         if (kv_nt) f.template operator()<true>();
         else f.template operator()<false>();
+      };
+      // V image of the bf16 pipe kernel: the line image (default), or
+      // LLMQ_DECODE_V_LINES=0 = the tr16 subtile image (A/B baseline and the
+      // equality test's other side). Read per call.
+      const char* vle = getenv("LLMQ_DECODE_V_LINES");
+      const bool v_lines = !(vle && atoi(vle) == 0);
+      const int pipe_nt = kv_nt_env <= 0 ? 0 : (kv_nt_env >= 2 && v_lines) ? 2 : 1;
+      auto dispatch_pipe_img = [&](auto&& f) {  // <KV_NT, V_LINES>
+        if (!v_lines) {
+          if (pipe_nt) f.template operator()<1, false>();
+          else f.template operator()<0, false>();
+        } else if (pipe_nt == 2) {
+          f.template operator()<2, true>();
+        } else if (pipe_nt == 1) {
+          f.template operator()<1, true>();
+        } else {
+          f.template operator()<0, true>();
+        }
       };
       // NREG: how many of a lane's 4 softmax registers hold q-heads with
       // the kernels' row placement (heads 4*reg .. 4*reg+3 in register reg):
@@ -524,10 +546,10 @@ void launch_decode(at::Tensor& out, const at::Tensor& q, const at::Tensor& kc,
             launch.template operator()<HD, F8>(
                 paged_decode_mfma_kernel<HD, 8, NREG, F8>);
           } else if (pipe) {
-            dispatch_kv_nt([&]<bool NT>() {
+            dispatch_pipe_img([&]<int NT, bool VL>() {
               launch.template operator()<HD, BF>(
-                  pipe_kt >= 128 ? paged_decode_pipe_kernel<HD, 8, 128, NREG, NT>
-                                 : paged_decode_pipe_kernel<HD, 8, 64, NREG, NT>);
+                  pipe_kt >= 128 ? paged_decode_pipe_kernel<HD, 8, 128, NREG, NT, VL>
+                                 : paged_decode_pipe_kernel<HD, 8, 64, NREG, NT, VL>);
             });
           } else {
             launch.template operator()<HD, BF>(

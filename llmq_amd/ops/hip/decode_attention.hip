@@ -619,8 +619,9 @@ __global__ __launch_bounds__(NW * WAVE) void paged_decode_mfma_kernel(
 //     into buf[(i+1)&1].
 //   - ALL staging is `global_load_lds` (no VGPR round-trip, no staging
 //     instructions on the VALU): the LDS image is lane-linear per wave
-//     instruction, so K's XOR swizzle and V's tr16 subtile permutation move
-//     to the per-lane SOURCE address (guide §5.4 rule 21).
+//     instruction, so K's XOR swizzle and V's image permutation (line image
+//     or tr16 subtile image, see V_LINES) move to the per-lane SOURCE
+//     address (guide §5.4 rule 21).
 //   - Raw `s_barrier` + counted `s_waitcnt vmcnt(N)`: V(i)+K(i+1) issue
 //     back-to-back right after the post-S barrier; the pre-PV barrier waits
 //     vmcnt(NI_K) (V landed, K still streaming); the loop-top barrier waits
@@ -637,16 +638,20 @@ __global__ __launch_bounds__(NW * WAVE) void paged_decode_mfma_kernel(
 // occupancy below that (the r1 lesson: this kernel is governed by
 // waves/SIMD, every latency trick that cost occupancy lost). The 128-key
 // chunk is 1 workgroup/CU by LDS (2 waves/SIMD) — let it use 196.
-// KV_NT: cache policy of the K DMAs (glds16<KV_NT>). The decode K/V stream
-// is read once per step, so the default instantiation streams K `nt` past L2
-// and the Infinity Cache: a K DMA consumes whole 128-byte lines (two 512-byte
-// key rows per instruction). The V DMAs keep the default policy: one of them
-// takes 32 bytes from each of 32 rows (a tr16 subtile), and the line's other
-// 96 bytes are the same wave's next three DMAs, which must hit the line in
-// L2; with `nt` on V the kernel measured 0.468 against 0.369 ms
-// (profiles/decode_kv_stream.md). Block-table loads, q loads and stores keep
-// the default policy too.
-template <int HEAD_DIM, int NW, int PD_KT, int NREG, bool KV_NT>
+// V_LINES: which LDS image V is staged in. false = the tr16 subtile image
+// (one V DMA takes 32 bytes from each of 32 cache rows); true = the line
+// image of attention_common.h (one V DMA takes eight whole 128-byte lines of
+// eight rows, 2 KiB less LDS per buffer pair). Same DMA count, same PV
+// operands and MFMA order: outputs are bitwise equal.
+// KV_NT: cache policy of the K/V DMAs. The decode K/V stream is read once per
+// step, so it can go `nt` past L2 and the Infinity Cache wherever ONE
+// instruction consumes the whole 128-byte line: 0 = default policy, 1 = K
+// `nt` (a K DMA covers two 512-byte key rows), 2 = K and V `nt` (line image
+// only: a subtile DMA leaves 96 bytes of every line to the same wave's next
+// three DMAs, which must hit the line in L2; with `nt` there the kernel
+// measured 0.468 against 0.369 ms, profiles/decode_kv_stream.md).
+// Block-table loads, q loads and stores keep the default policy.
+template <int HEAD_DIM, int NW, int PD_KT, int NREG, int KV_NT, bool V_LINES>
 __global__ __launch_bounds__(NW * WAVE, (PD_KT <= 64 ? 4 : 2)) void paged_decode_pipe_kernel(
     __hip_bfloat16* __restrict__ out,      // [B, H, D]
     const __hip_bfloat16* __restrict__ q,  // [B, H, D]
@@ -665,11 +670,18 @@ __global__ __launch_bounds__(NW * WAVE, (PD_KT <= 64 ? 4 : 2)) void paged_decode
   constexpr int DT = D4 / 16;       // 16-dim MFMA tiles per wave
   constexpr int CPK = D / 8;        // 16B granules per key row
   constexpr int NI_K = PD_KT * CPK / NT;          // K glds per wave per chunk
-  constexpr int NSUB = v_img_nsub(PD_KT, D);      // V tr-subtiles per chunk
+  // V DMAs per chunk: tr-subtiles, or 8-key × 64-dim pieces (as many)
+  constexpr int NSUB = V_LINES ? v_line_npiece(PD_KT, D) : v_img_nsub(PD_KT, D);
   constexpr int NI_V = NSUB / NW;                 // V glds per wave per chunk
-  constexpr int KV_ELEMS = kv_tile_elems(PD_KT, D);
+  constexpr int KV_ELEMS = V_LINES ? PD_KT * D : kv_tile_elems(PD_KT, D);
+  constexpr int PPO = D / 64;                     // line image: pieces per key octet
+  constexpr int NVB = v_line_nbase<D, DT>();
   static_assert(PD_KT % 32 == 0 && SLABS <= NW && NSUB % NW == 0, "");
   static_assert(PD_KT * CPK % NT == 0 && D % NW == 0 && D4 % 16 == 0, "");
+  static_assert(!V_LINES || (v_line_layout_ok_v<PD_KT, D, DT> &&
+                             v_line_elems(PD_KT, D) <= KV_ELEMS),
+                "V line image layout");
+  static_assert(V_LINES || KV_NT < 2, "the subtile image cannot stream V nt");
 
   const int b = blockIdx.x;
   const int kh = blockIdx.y;
@@ -761,8 +773,9 @@ __global__ __launch_bounds__(NW * WAVE, (PD_KT <= 64 ? 4 : 2)) void paged_decode
     return k_cache + head_off + blk * blk_stride + ((gkey & bs_mask) * D + d);
   };
   // V: subtile st, in-subtile granule = lane (tr16 image inverse mapping).
+  // Line image: piece st, in-piece slot = lane (v_line_source).
   auto v_src = [&](int base, int st) -> const __hip_bfloat16* {
-    const VImgSrc s = v_img_source<D>(st, lane);
+    const VImgSrc s = V_LINES ? v_line_source<D>(st, lane) : v_img_source<D>(st, lane);
     const int gkey = min(base + s.key, L - 1);
     const long blk = bt_l[gkey >> bs_shift];
     return v_cache + head_off + blk * blk_stride + ((gkey & bs_mask) * D + s.dim);
@@ -778,23 +791,44 @@ __global__ __launch_bounds__(NW * WAVE, (PD_KT <= 64 ? 4 : 2)) void paged_decode
 #pragma unroll
     for (int j = 0; j < NI_K; ++j) {
       const int off = __builtin_amdgcn_readfirstlane((wid * NI_K + j) * 512);
-      glds16<KV_NT>(src[j], dst + off);
+      glds16<(KV_NT >= 1)>(src[j], dst + off);
     }
   };
   // A wave's NI_V subtiles are consecutive 16-dim tiles of ONE 32-key group,
   // so its lanes read the same cache row for all of them: one row address
   // per chunk, then a 16-element step per subtile (v_img_source's key/dim
   // progression, part of the compile-time layout check).
-  static_assert((D / 16) % NI_V == 0, "a wave's V subtiles share their keys");
+  // Line image: a wave's NI_V pieces are the PPO pieces of NI_V/PPO whole key
+  // octets (one for 64-key chunks, two for 128), so again one row address
+  // per octet and a 64-element step per piece, each DMA eight whole lines.
+  static_assert(V_LINES || (D / 16) % NI_V == 0, "a wave's V subtiles share their keys");
+  static_assert(!V_LINES || NI_V % PPO == 0, "a wave's V pieces are whole key octets");
   auto issue_v = [&](int base, short* dst) {
-    const __hip_bfloat16* const row = v_src(base, wid * NI_V);
+    if constexpr (V_LINES) {
+      const __hip_bfloat16* row[NI_V / PPO];
 #pragma unroll
-    for (int j = 0; j < NI_V; ++j) {
-      const int off =
-          __builtin_amdgcn_readfirstlane((wid * NI_V + j) * V_SUB_STRIDE);
-      glds16(row + j * 16, dst + off);  // default policy: see KV_NT
+      for (int oo = 0; oo < NI_V / PPO; ++oo) row[oo] = v_src(base, wid * NI_V + oo * PPO);
+#pragma unroll
+      for (int j = 0; j < NI_V; ++j) {
+        const int off =
+            __builtin_amdgcn_readfirstlane((wid * NI_V + j) * V_PIECE_ELEMS);
+        glds16<(KV_NT >= 2)>(row[j / PPO] + (j % PPO) * 64, dst + off);
+      }
+    } else {
+      const __hip_bfloat16* const row = v_src(base, wid * NI_V);
+#pragma unroll
+      for (int j = 0; j < NI_V; ++j) {
+        const int off =
+            __builtin_amdgcn_readfirstlane((wid * NI_V + j) * V_SUB_STRIDE);
+        glds16(row + j * 16, dst + off);  // default policy: see KV_NT
+      }
     }
   };
+  // Line image: this lane's PV read bases for the wave's dim slab, in
+  // elements; a PV read is base + compile-time offset (v_line_rd_off).
+  int vb[NVB];
+#pragma unroll
+  for (int i = 0; i < NVB; ++i) vb[i] = v_line_rd_base<D>(wid * DT, i, lane);
   // ---- prologue: block table visible, then K(first) in flight
   pipe_barrier();  // bt_l ready (plain ds_writes; lgkm drain)
   if (range_lo < range_hi) issue_k(range_lo, kv0);
@@ -837,7 +871,10 @@ __global__ __launch_bounds__(NW * WAVE, (PD_KT <= 64 ? 4 : 2)) void paged_decode
     }
 
     // ---- OT[dims,16q] += V^T P^T over this wave's dim slab
-    attn_pv_tile<D, PD_KT, DT>(X, p_lds2, alpha_s, rescale, ot, wid * DT, lane);
+    if constexpr (V_LINES)
+      attn_pv_tile_lines<D, PD_KT, DT>(X, vb, p_lds2, alpha_s, rescale, ot, lane);
+    else
+      attn_pv_tile<D, PD_KT, DT>(X, p_lds2, alpha_s, rescale, ot, wid * DT, lane);
     // No trailing barrier: the next loop-top barrier (vmcnt(0)) both
     // protects X against the glds of chunk base+2 (issued only after the
     // NEXT post-S barrier) and confirms K(next) landed in Y.
