@@ -29,6 +29,7 @@ _CONTROL_FIELDS = (
     "presence_penalty",
     "frequency_penalty",
     "min_p",
+    "logprobs",
 )
 
 
@@ -56,6 +57,8 @@ class Job(BaseModel):
     presence_penalty: Optional[float] = Field(None)
     frequency_penalty: Optional[float] = Field(None)
     min_p: Optional[float] = Field(None)
+    logprobs: Optional[int] = Field(
+        None, description="Return token logprobs with this many alternatives (0-20)")
 
     @model_validator(mode="after")
     def _exactly_one_input(self) -> "Job":
@@ -103,6 +106,11 @@ class Result(BaseModel):
     cached_tokens: Optional[int] = Field(None, description="Prompt tokens served from the prefix cache")
     output_tokens: Optional[int] = Field(None)
     finish_reason: Optional[str] = Field(None, description="stop | length | eos")
+    # Jobs that asked for logprobs: one {"token_id", "token", "logprob", "rank",
+    # "top_logprobs": [{"token_id", "token", "logprob"}]} per output token,
+    # and the sum of the tokens' logprobs.
+    logprobs: Optional[List[Dict[str, Any]]] = Field(None)
+    cumulative_logprob: Optional[float] = Field(None)
 
 
 class QueueStats(BaseModel):

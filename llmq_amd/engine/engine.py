@@ -16,7 +16,7 @@ from __future__ import annotations
 import logging
 import os
 import time
-from dataclasses import dataclass, field
+from dataclasses import dataclass, field, replace
 from typing import Dict, List, Optional
 
 import torch
@@ -88,6 +88,13 @@ class RequestOutput:
     queue_wait_ms: Optional[float] = None
     prefill_ms: Optional[float] = None
     decode_ms: Optional[float] = None
+    # SamplingParams.logprobs set: this step's entry (token_id, logprob, rank,
+    # [(id, logprob) x k]); on the finishing output also every entry of the
+    # request (one per output token, EOS and stop-string tokens included) and
+    # their sum
+    new_logprobs: Optional[tuple] = None
+    logprobs: Optional[List[tuple]] = None
+    cumulative_logprob: Optional[float] = None
 
 
 class LLMEngine:
@@ -278,6 +285,8 @@ class LLMEngine:
         if request_id in self._seqs:
             raise ValueError(f"duplicate request_id {request_id}")
         params = params or SamplingParams()
+        if params.logprobs is not None and params.logprobs > self.spec.vocab_size:
+            params = replace(params, logprobs=self.spec.vocab_size)
         if prompt_token_ids is None:
             if prompt is None:
                 raise ValueError("need prompt or prompt_token_ids")
@@ -325,6 +334,8 @@ class LLMEngine:
             return []
         self.last_step_kind = batch.kind
         t0 = time.perf_counter()
+        take_lp = self.runner.take_logprobs
+        lp_parts = None  # split mixed step: (decode, prefill) logprob rows
         if batch.kind == "prefill":
             tokens = self.runner.execute_prefill(batch.seqs, batch.chunks or None)
         elif batch.kind == "mixed":
@@ -357,15 +368,28 @@ class LLMEngine:
                     cur.wait_stream(ds)
                     d_tokens.record_stream(cur)
                     tokens = torch.cat([d_tokens, p_tokens])
+                    # only now: the decode results were copied on ds
+                    lp_parts = (take_lp("main"), take_lp("prefill"))
                 else:
                     d_tokens = self.runner.execute_decode(dseqs).clone()
+                    # both calls sample into "main": collect in between
+                    d_lp = take_lp("main")
                     p_tokens = self.runner.execute_prefill(pseqs, batch.chunks)
                     tokens = torch.cat([d_tokens, p_tokens])
+                    lp_parts = (d_lp, take_lp("main"))
+                sizes = (d_tokens.numel(), p_tokens.numel())
             else:
                 tokens = self.runner.execute_mixed(batch)
         else:
             tokens = self.runner.execute_decode(batch.seqs)
         token_list = tokens.tolist()
+        if lp_parts is None:
+            row_lps = take_lp("main")
+        elif lp_parts[0] is None and lp_parts[1] is None:
+            row_lps = None
+        else:
+            row_lps = [e for part, n in zip(lp_parts, sizes)
+                       for e in (part or [None] * n)]
         now = time.time()
         self.steps += 1
         outputs: List[RequestOutput] = []
@@ -395,6 +419,10 @@ class LLMEngine:
                 if seq.first_token_time is None:
                     seq.first_token_time = now
             seq.token_ids.append(tok)
+            entry = None
+            if seq.logprobs is not None:
+                entry = row_lps[row]
+                seq.logprobs.append(entry)
             params = seq.params
             nt = len(seq.token_ids)
             out = RequestOutput(
@@ -403,6 +431,7 @@ class LLMEngine:
                 prompt_tokens=seq.prompt_len,
                 output_tokens=nt - seq.prompt_len,
                 cached_tokens=seq.cached_tokens,
+                new_logprobs=entry,
             )
             # Cheap pre-check: most decode steps finish nothing; only take
             # the full _check_finish path (stop-string decode etc.) when a
@@ -419,6 +448,9 @@ class LLMEngine:
                 out.finished = True
                 out.finish_reason = reason
                 out.text = self._final_text(seq)
+                if seq.logprobs is not None:
+                    out.logprobs = seq.logprobs
+                    out.cumulative_logprob = float(sum(e[1] for e in seq.logprobs))
                 prefill_at = self._prefill_done_at.pop(seq.request_id, now)
                 started = seq.prefill_start_time or prefill_at
                 out.queue_wait_ms = (started - seq.arrival_time) * 1000.0

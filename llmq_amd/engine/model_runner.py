@@ -33,6 +33,22 @@ from llmq_amd.engine.scheduler import ScheduledBatch, Sequence
 
 logger = logging.getLogger(__name__)
 
+# One packed int32 record per row that asked for logprobs: 1 + MAX_LOGPROBS
+# token ids, as many fp32 logprobs (bit patterns), and the rank.
+_LP_W = 1 + ops.MAX_LOGPROBS
+_LP_PACK = 2 * _LP_W + 1
+
+
+def _logprob_entries(ids, lp, rank, ks) -> List[tuple]:
+    """Per-row (token_id, logprob, rank, [(id, logprob) x k]) from the arrays
+    of ops.token_logprobs, each row cut to the k it asked for."""
+    ids, lp, rank = ids.tolist(), lp.tolist(), rank.tolist()
+    return [
+        (ids[j][0], lp[j][0], rank[j],
+         list(zip(ids[j][1:1 + k], lp[j][1:1 + k])))
+        for j, k in enumerate(ks)
+    ]
+
 
 def _buckets(max_bs: int) -> List[int]:
     sizes = [1, 2, 4, 8, 16, 24, 32, 48, 64, 96, 128, 192, 256, 384, 512]
@@ -71,6 +87,10 @@ class ModelRunner:
         # decode path, "prefill" for the prefill segment of an OVERLAPPED
         # split mixed step — two concurrent streams must not share them).
         self._sample_bufs: Dict[str, Dict[str, torch.Tensor]] = {}
+        # Token logprobs of the latest _sample call per buffer name, until
+        # take_logprobs collects them: (asking rows, their k, batch size,
+        # then either the entries (CPU) or the pinned record + copy event).
+        self._logprobs: Dict[str, tuple] = {}
         # Count table of the repetition/presence/frequency penalties; holds no
         # memory until the first penalised request (PenaltyTable docstring).
         self.penalty_table = PenaltyTable(
@@ -414,6 +434,13 @@ class ModelRunner:
                 "slots_h": torch.empty(cap, dtype=torch.int32, pin_memory=True),
                 "pen": torch.empty(cap, 3, dtype=torch.float32, device=dev),
                 "pen_h": torch.empty(cap, 3, dtype=torch.float32, pin_memory=True),
+                # token logprobs: the rows that asked, and one packed int32
+                # record per row (ids | lp bits | rank) so that the results
+                # reach the host in a single copy
+                "lp_rows": torch.empty(cap, dtype=torch.int32, device=dev),
+                "lp_rows_h": torch.empty(cap, dtype=torch.int32, pin_memory=True),
+                "lp_pack": torch.empty(cap, _LP_PACK, dtype=torch.int32, device=dev),
+                "lp_pack_h": torch.empty(cap, _LP_PACK, dtype=torch.int32, pin_memory=True),
             }
             self._sample_bufs[name] = buf
         return buf
@@ -445,6 +472,10 @@ class ModelRunner:
                 buf_name: str = "main", softcap: float = 0.0) -> torch.Tensor:
         dev = logits.device
         self._sample_step += 1
+        self._logprobs.pop(buf_name, None)
+        V = logits.size(1)
+        lp_rows = [i for i, s in enumerate(seqs) if s.params.logprobs is not None]
+        lp_ks = [min(seqs[i].params.logprobs, ops.MAX_LOGPROBS, V) for i in lp_rows]
         simple = all(
             s.params.top_k == 0 and s.params.top_p >= 1.0 and s.params.min_p <= 0.0
             for s in seqs
@@ -515,7 +546,27 @@ class ModelRunner:
             if penalised:
                 self.penalty_table.count_sampled(
                     seqs, buf["slots"][:B], buf["out"][:B])
+            if lp_rows:
+                # One more read of the asking rows, of the logits the sampler
+                # read (before penalties and temperature): one launch and one
+                # device-to-host copy, on this call's stream.
+                R, K = len(lp_rows), max(lp_ks)
+                rh = buf["lp_rows_h"]
+                for j, i in enumerate(lp_rows):
+                    rh[j] = i
+                buf["lp_rows"][:R].copy_(rh[:R], non_blocking=True)
+                pack = buf["lp_pack"]
+                ops.token_logprobs(
+                    logits_f, buf["out"][:B], K, softcap, rows=buf["lp_rows"][:R],
+                    out=(pack[:R, : 1 + K],
+                         pack[:R, _LP_W : _LP_W + 1 + K].view(torch.float32),
+                         pack[:R, 2 * _LP_W]))
+                buf["lp_pack_h"][:R].copy_(pack[:R], non_blocking=True)
+                done = torch.cuda.Event()
+                done.record()
+                self._logprobs[buf_name] = (lp_rows, lp_ks, B, buf["lp_pack_h"], done)
             return buf["out"][:B]
+        raw_logits = logits
         if penalised:
             # CPU: the specification itself, from the token histories
             logits = self._penalised_logits_cpu(logits, seqs)
@@ -547,4 +598,35 @@ class ModelRunner:
                     tks_c[j : j + 1], g, mps_c[j : j + 1],
                 )[0]
             out[idx] = redraw.to(out.device)
+        if lp_rows:
+            # CPU: the specification, on the logits before penalties
+            ids, lp, rank = torch_ref.token_logprobs(
+                raw_logits, out, max(lp_ks), softcap,
+                rows=torch.tensor(lp_rows, dtype=torch.int32))
+            self._logprobs[buf_name] = (
+                lp_rows, lp_ks, len(seqs), _logprob_entries(ids, lp, rank, lp_ks))
+        return out
+
+    def take_logprobs(self, buf_name: str = "main") -> Optional[List[Optional[tuple]]]:
+        """Token logprobs of the latest _sample call on `buf_name`, once: one
+        entry per sampled row, (token_id, logprob, rank, [(id, logprob) x k])
+        for rows that asked and None for the others; None when no row asked.
+        On the GPU this waits for that call's result copy, so in an overlapped
+        step call it after the streams have joined."""
+        res = self._logprobs.pop(buf_name, None)
+        if res is None:
+            return None
+        rows, ks, B = res[:3]
+        if len(res) == 4:
+            entries = res[3]
+        else:
+            host, done = res[3:]
+            done.synchronize()
+            rec = host[: len(rows)].numpy()
+            entries = _logprob_entries(
+                rec[:, :_LP_W], rec[:, _LP_W : 2 * _LP_W].view(np.float32),
+                rec[:, 2 * _LP_W], ks)
+        out: List[Optional[tuple]] = [None] * B
+        for i, e in zip(rows, entries):
+            out[i] = e
         return out

@@ -10,6 +10,9 @@ from dataclasses import dataclass, field
 from typing import List, Optional
 
 
+MAX_LOGPROBS = 20  # the token_logprobs kernel's top-k limit
+
+
 @dataclass
 class SamplingParams:
     temperature: float = 0.7
@@ -28,6 +31,11 @@ class SamplingParams:
     frequency_penalty: float = 0.0
     # keep tokens with probability >= min_p x the most likely token's
     min_p: float = 0.0  # 0 = off
+    # Return the log-probability and rank of every generated token plus the
+    # `logprobs` most likely alternatives (0 = the token alone, None = off),
+    # under log_softmax of the model's (soft-capped) logits: before penalties,
+    # temperature and top-k/top-p/min_p.
+    logprobs: Optional[int] = None
 
     def __post_init__(self) -> None:
         if self.temperature < 0:
@@ -46,6 +54,8 @@ class SamplingParams:
             raise ValueError("frequency_penalty must be in [-2, 2]")
         if not 0.0 <= self.min_p <= 1.0:
             raise ValueError("min_p must be in [0, 1]")
+        if self.logprobs is not None and not 0 <= self.logprobs <= MAX_LOGPROBS:
+            raise ValueError(f"logprobs must be in [0, {MAX_LOGPROBS}]")
 
     @property
     def greedy(self) -> bool:

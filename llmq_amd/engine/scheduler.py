@@ -47,7 +47,7 @@ class Sequence:
         "request_id", "token_ids", "prompt_len", "params", "status",
         "block_table", "arrival_time", "first_token_time", "finish_reason",
         "output_text", "num_preemptions", "prefilled", "prefill_start_time",
-        "uid", "cached_tokens",
+        "uid", "cached_tokens", "logprobs",
     )
 
     def __init__(self, request_id: str, prompt_token_ids: List[int], params: SamplingParams,
@@ -71,6 +71,10 @@ class Sequence:
         self.prefilled = 0  # context tokens whose KV is in the cache
         self.prefill_start_time: Optional[float] = None
         self.cached_tokens = 0  # prefix-cache hit of the latest admission
+        # params.logprobs set: one (token_id, logprob, rank, [(id, logprob)])
+        # per generated token; like token_ids it survives preemption
+        self.logprobs: Optional[List[tuple]] = (
+            [] if params.logprobs is not None else None)
 
     @property
     def num_tokens(self) -> int:

@@ -405,6 +405,48 @@ def penalty_count_tokens(
     table.index_put_((s, t), torch.where((words & 0x7FFF) == 0x7FFF, words, words + 1))
 
 
+MAX_LOGPROBS = torch_ref.MAX_LOGPROBS
+
+
+def token_logprobs(
+    logits: torch.Tensor,   # [B, V] fp32, or bf16/fp16 as the GEMM wrote them
+    tokens: torch.Tensor,   # [B] int64 sampled tokens
+    k: int,                 # alternatives per row, 0..min(MAX_LOGPROBS, V)
+    softcap: float = 0.0,   # > 0: logprobs of cap * tanh(logit / cap)
+    rows: Optional[torch.Tensor] = None,  # [R] int32 rows that asked (None = all)
+    out: Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]] = None,
+    threads: int = 0,       # workgroup size of the kernel, 0 = default
+) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(ids [R, 1+k] int32, lp [R, 1+k] fp32, rank [R] int32) of
+    torch_ref.token_logprobs: the sampled token's log-probability under
+    log_softmax of the soft-capped logits, its rank, and the k most likely
+    tokens in (value descending, index ascending) order. On the GPU one
+    kernel, one workgroup per requested row, reading each logit once; no
+    launch when no row asked. `out` = (ids, lp, rank) tensors to fill, which
+    may be column slices of a wider buffer."""
+    V = logits.size(1)
+    assert 0 <= k <= min(MAX_LOGPROBS, V), f"k={k} outside [0, min({MAX_LOGPROBS}, {V})]"
+    if not _use_hip(logits):
+        res = torch_ref.token_logprobs(logits, tokens, k, softcap, rows)
+        if out is None:
+            return res
+        for dst, src in zip(out, res):
+            dst.copy_(src)
+        return out
+    dev = logits.device
+    if rows is None:
+        rows = torch.arange(logits.size(0), dtype=torch.int32, device=dev)
+    R = rows.numel()
+    if out is None:
+        out = (torch.empty(R, 1 + k, dtype=torch.int32, device=dev),
+               torch.empty(R, 1 + k, dtype=torch.float32, device=dev),
+               torch.empty(R, dtype=torch.int32, device=dev))
+    ids, lp, rank = out
+    if R:
+        _EXT.token_logprobs(lp, ids, rank, logits, rows, tokens, k, softcap, threads)
+    return out
+
+
 def sample_tokens(
     logits: torch.Tensor,
     temperatures: torch.Tensor,

@@ -918,9 +918,64 @@ void penalty_count_tokens(at::Tensor table, at::Tensor slots, at::Tensor tokens)
                      (int)table.size(0), (long)table.size(1));
 }
 
+// Logprob of tokens[rows[r]], its rank and the K most likely tokens of row
+// rows[r], for each requested row r (torch_ref.token_logprobs), on the
+// current stream. The outputs may be column slices of wider buffers.
+// threads: workgroup size, 0 = the default.
+void token_logprobs(at::Tensor lp_out, at::Tensor ids_out, at::Tensor rank_out,
+                    at::Tensor logits, at::Tensor rows, at::Tensor tokens,
+                    long K, double softcap, long threads) {
+  CHECK_GPU(logits);
+  CHECK_GPU(rows);
+  CHECK_GPU(tokens);
+  CHECK_GPU(lp_out);
+  CHECK_GPU(ids_out);
+  CHECK_GPU(rank_out);
+  CHECK_LASTDIM(logits);
+  TORCH_CHECK(logits.dim() == 2);
+  const int B = logits.size(0), V = logits.size(1);
+  const long R = rows.numel();
+  TORCH_CHECK(B >= 1 && V >= 1);
+  TORCH_CHECK(K >= 0 && K <= LP_MAX_K && K <= V, "token_logprobs: K must be in "
+              "[0, min(", LP_MAX_K, ", V)], got ", K);
+  TORCH_CHECK(rows.scalar_type() == at::kInt && rows.is_contiguous());
+  TORCH_CHECK(tokens.scalar_type() == at::kLong && tokens.is_contiguous() &&
+              tokens.numel() == B);
+  TORCH_CHECK(lp_out.scalar_type() == at::kFloat && lp_out.dim() == 2 &&
+              lp_out.size(0) == R && lp_out.size(1) == 1 + K);
+  TORCH_CHECK(ids_out.scalar_type() == at::kInt && ids_out.dim() == 2 &&
+              ids_out.size(0) == R && ids_out.size(1) == 1 + K);
+  TORCH_CHECK(rank_out.scalar_type() == at::kInt && rank_out.dim() == 1 &&
+              rank_out.size(0) == R);
+  CHECK_LASTDIM(lp_out);
+  CHECK_LASTDIM(ids_out);
+  TORCH_CHECK(threads == 0 || threads == 512 || threads == 1024,
+              "token_logprobs: threads must be 0, 512 or 1024");
+  if (R == 0) return;
+  dispatch_dtype(logits, "token_logprobs", [&]<typename T>() {
+    auto launch = [&](auto kernel, int nt) {
+      hipLaunchKernelGGL(
+          kernel, dim3(R), dim3(nt), 0, stream(), lp_out.data_ptr<float>(),
+          ids_out.data_ptr<int>(), rank_out.data_ptr<int>(),
+          reinterpret_cast<const T*>(logits.data_ptr()), rows.data_ptr<int>(),
+          tokens.data_ptr<long>(), B, V, logits.stride(0), (int)K,
+          lp_out.stride(0), ids_out.stride(0), rank_out.stride(0),
+          (float)softcap, softcap_reciprocal(softcap));
+    };
+    if (threads == 512) {
+      if (K > 0) launch(token_logprobs_kernel<T, 512, true>, 512);
+      else launch(token_logprobs_kernel<T, 512, false>, 512);
+    } else {
+      if (K > 0) launch(token_logprobs_kernel<T, 1024, true>, 1024);
+      else launch(token_logprobs_kernel<T, 1024, false>, 1024);
+    }
+  });
+}
+
 }  // namespace
 
 TORCH_LIBRARY(llmq_amd, m) {
+  m.def("token_logprobs(Tensor(a!) lp_out, Tensor(b!) ids_out, Tensor(c!) rank_out, Tensor logits, Tensor rows, Tensor tokens, int K, float softcap=0.0, int threads=0) -> ()");
   m.def("rmsnorm(Tensor(a!) out, Tensor input, Tensor weight, float eps, float offset) -> ()");
   m.def("fused_add_rmsnorm(Tensor(a!) x, Tensor(b!) residual, Tensor weight, float eps, float offset) -> ()");
   m.def("silu_and_mul(Tensor(a!) out, Tensor input) -> ()");
@@ -951,6 +1006,7 @@ TORCH_LIBRARY_IMPL(llmq_amd, CUDA, m) {
   m.impl("sample_gumbel_argmax", &sample_gumbel_argmax);
   m.impl("topk_topp_bound", &topk_topp_bound);
   m.impl("penalty_count_tokens", &penalty_count_tokens);
+  m.impl("token_logprobs", &token_logprobs);
   m.impl("skinny_gemm", &skinny_gemm);
   m.impl("norm_add_norm", &norm_add_norm);
   m.impl("rope_and_cache", &rope_and_cache);

@@ -464,3 +464,273 @@ __global__ void unpack_keys_kernel(long* __restrict__ out,
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b < B) out[b] = (long)(unsigned int)(~(keys[b] & 0xffffffffu));
 }
+
+// ------------------------------------------------------- token logprobs --
+// Log-probability of the sampled token, its rank, and the K most likely
+// alternatives, from one more read of a logits row: the specification is
+// torch_ref.token_logprobs. One workgroup per requested row; every logit is
+// loaded once, walked like the sampler walks it (scalar head to the first
+// 16-byte boundary, 16-byte vectors, scalar tail).
+//
+// The vocabulary order is pack_key's: value descending, ties toward the lower
+// index (-0 is folded onto +0 first, as a sort sees them equal). Each thread
+// keeps an online (max, sum of exp) pair and counts the keys above the
+// token's; the top K live in LDS: an element whose key exceeds the threshold
+// `thr` is appended to a candidate buffer, and when the buffer could no
+// longer take a whole tile it is compacted to its K largest keys (lp_select),
+// with thr = the K-th. thr starts just below the K-th largest of the first
+// tile's group maxima (lp_seed_threshold).
+// Invariant: at most LP_SLACK candidates before a tile, and a tile appends at
+// most TILE, so CAP = LP_SLACK + TILE never overflows. On random rows the
+// walk appends ~ K ln(V / K) candidates and only the final compaction runs;
+// an ascending row compacts on every tile, slowly but correctly.
+
+#define LP_MAX_K 20
+#define LP_SLACK 1024
+#define LP_RANK_MAX 1024
+
+DEVINL float unpack_key_value(unsigned long long key) {
+  unsigned int u = (unsigned int)(key >> 32);
+  u = (u & 0x80000000u) ? (u & 0x7fffffffu) : ~u;
+  return __uint_as_float(u);
+}
+
+DEVINL unsigned long long wave_reduce_max_u64(unsigned long long x) {
+#pragma unroll
+  for (int off = WAVE / 2; off > 0; off >>= 1) {
+    const unsigned long long o = __shfl_xor(x, off, WAVE);
+    x = o > x ? o : x;
+  }
+  return x;
+}
+
+// Selects the `rounds` largest of keys[0, n) into win[0, rounds), in
+// descending order. Up to LP_RANK_MAX keys by counting: the thread that holds
+// a key counts the keys above it, and that count is the key's place (keys
+// differ, or are 0 and at the bottom, where equal places hold equal values).
+// All lanes read the same address, so the LDS reads are broadcasts, and there
+// is one barrier; the work is n^2 compares, ~1 us at the few hundred
+// candidates a random row leaves. Beyond that by `rounds` rounds of workgroup
+// argmax, each below the previous winner (~1.7 us per round). `win` is all
+// zero on entry; n >= rounds >= 1, uniform.
+template <int NT>
+DEVINL void lp_select(const unsigned long long* keys, unsigned long long* win,
+                      int n, int rounds) {
+  const int tid = threadIdx.x;
+  if (n <= LP_RANK_MAX) {
+    for (int i = tid; i < n; i += NT) {
+      const unsigned long long k = keys[i];
+      int place = 0;
+      for (int j = 0; j < n; ++j) place += keys[j] > k ? 1 : 0;
+      if (place < rounds) win[place] = k;
+    }
+    __syncthreads();
+    return;
+  }
+  unsigned long long prev = ~0ull;
+  for (int r = 0; r < rounds; ++r) {
+    unsigned long long best = 0;
+    for (int i = tid; i < n; i += NT) {
+      const unsigned long long k = keys[i];
+      if (k < prev && k > best) best = k;
+    }
+    best = wave_reduce_max_u64(best);
+    if ((tid & (WAVE - 1)) == 0 && best) atomicMax(&win[r], best);
+    __syncthreads();
+    prev = win[r];
+  }
+}
+
+// Keeps the min(K, n) largest of keys[0, n) at the front, in descending
+// order, and sets *n_keys to that number. `n` and `K` are uniform, `win` is
+// all zero on entry and on return. Returns the new threshold: the K-th
+// largest key, or 0 while fewer than K exist.
+template <int NT>
+DEVINL unsigned long long lp_compact(unsigned long long* keys,
+                                     unsigned long long* win, int* n_keys,
+                                     int n, int K) {
+  const int tid = threadIdx.x;
+  const int rounds = min(K, n);
+  if (rounds == 0) return 0ull;
+  lp_select<NT>(keys, win, n, rounds);
+  const unsigned long long mine = tid < rounds ? win[tid] : 0ull;
+  const unsigned long long kth = win[rounds - 1];
+  __syncthreads();
+  if (tid < rounds) { keys[tid] = mine; win[tid] = 0ull; }
+  if (tid == 0) *n_keys = rounds;
+  __syncthreads();
+  return rounds == K ? kth : 0ull;
+}
+
+// A first threshold before the walk, while the candidate buffer is empty:
+// the maxima of the first tile's groups of four vectors (0 = group without
+// one) go through the buffer, and the threshold is their K-th largest, less
+// one. At least K keys of the row are above it, so nothing of the row's top
+// K is lost, and on a random row the first tile appends a few dozen
+// candidates instead of all of its elements. 0 while fewer than K groups
+// hold a key. `win` is all zero on entry and on return, *n_keys stays 0.
+template <int NT>
+DEVINL unsigned long long lp_seed_threshold(unsigned long long mine,
+                                            unsigned long long* keys,
+                                            unsigned long long* win, int K) {
+  const int tid = threadIdx.x;
+#pragma unroll
+  for (int off = 1; off < 4; off <<= 1) {
+    const unsigned long long o = __shfl_xor(mine, off, WAVE);
+    mine = o > mine ? o : mine;
+  }
+  if ((tid & 3) == 0) keys[tid >> 2] = mine;
+  __syncthreads();
+  lp_select<NT>(keys, win, NT / 4, K);
+  const unsigned long long kth = win[K - 1];
+  __syncthreads();
+  if (tid < LP_MAX_K) win[tid] = 0ull;
+  __syncthreads();
+  return kth ? kth - 1 : 0ull;
+}
+
+template <typename T, int NT, bool TOPK>
+__global__ __launch_bounds__(NT) void token_logprobs_kernel(
+    float* __restrict__ lp_out,    // [R, 1+K], row stride lp_stride
+    int* __restrict__ ids_out,     // [R, 1+K], row stride ids_stride
+    int* __restrict__ rank_out,    // [R], stride rank_stride
+    const T* __restrict__ logits,  // [B, V], row stride `stride`
+    const int* __restrict__ rows,  // [R] batch rows that asked
+    const long* __restrict__ tokens,  // [B] sampled tokens
+    int B, int V, long stride, int K, long lp_stride, long ids_stride,
+    long rank_stride, float softcap, float inv_cap) {
+  constexpr int VE = Vec8<T>::kElems;
+  constexpr int TILE = NT * VE;
+  constexpr int CAP = TOPK ? LP_SLACK + TILE : 1;
+  constexpr int NW = NT / WAVE;
+  static_assert(NT >= LP_MAX_K && LP_SLACK >= LP_MAX_K + 2 * 8);
+  __shared__ unsigned long long keys[CAP];
+  __shared__ unsigned long long win[LP_MAX_K];
+  __shared__ int n_keys;
+  __shared__ float red_m[NW], red_s[NW];
+  __shared__ int red_c[NW];
+  __shared__ float sh_lse;
+
+  const int r = blockIdx.x;
+  const int tid = threadIdx.x;
+  const int b = min(max(rows[r], 0), B - 1);
+  const T* row = logits + (long)b * stride;
+  const int tok = (int)min(max(tokens[b], 0L), (long)V - 1);
+  const float c = logit_value(row[tok], softcap, inv_cap) + 0.0f;
+  const unsigned long long ckey = pack_key(c, tok);
+
+  if constexpr (TOPK) {
+    if (tid < LP_MAX_K) win[tid] = 0ull;
+    if (tid == 0) n_keys = 0;
+    __syncthreads();
+  }
+  float m = -3e38f, s = 0.f;
+  int above = 0;
+  unsigned long long thr = 0ull;  // uniform; below every key
+
+  // l is at most the running max m
+  auto visit = [&](int v, float l) {
+    s += __expf(l - m);
+    const unsigned long long key = pack_key(l, v);
+    above += key > ckey ? 1 : 0;
+    if constexpr (TOPK) {
+      if (key > thr) {
+        const int p = atomicAdd(&n_keys, 1);
+        if (p < CAP) keys[p] = key;
+      }
+    }
+  };
+  auto visit_one = [&](int v, T raw) {
+    const float l = logit_value(raw, softcap, inv_cap) + 0.0f;
+    if (l > m) { s *= __expf(m - l); m = l; }
+    visit(v, l);
+  };
+
+  const int mis = (int)(((unsigned long)row / sizeof(T)) % VE);
+  const int vb = min(V, mis ? VE - mis : 0);
+  const int ve = vb + (V - vb) / VE * VE;
+  int v = vb + tid * VE;
+  Vec8<T> cur;
+  if (v < ve) cur = load16(row + v);
+  if constexpr (TOPK) {
+    unsigned long long mine = 0ull;
+    if (v < ve) {
+#pragma unroll
+      for (int j = 0; j < VE; ++j) {
+        const unsigned long long key = pack_key(
+            logit_value(cur.data[j], softcap, inv_cap) + 0.0f, v + j);
+        mine = key > mine ? key : mine;
+      }
+    }
+    thr = lp_seed_threshold<NT>(mine, keys, win, K);
+  }
+  if (tid < vb) visit_one(tid, row[tid]);
+  // Tiles of NT vectors, the next tile's load issued before this tile's work.
+  // The trip count is uniform, so the barriers are legal.
+  for (int base = vb; base < ve; base += TILE, v += TILE) {
+    Vec8<T> nxt;
+    if (v + TILE < ve) nxt = load16(row + v + TILE);
+    if (v < ve) {
+      float l[VE];
+#pragma unroll
+      for (int j = 0; j < VE; ++j)
+        l[j] = logit_value(cur.data[j], softcap, inv_cap) + 0.0f;
+      float vm = l[0];
+#pragma unroll
+      for (int j = 1; j < VE; ++j) vm = fmaxf(vm, l[j]);
+      if (vm > m) { s *= __expf(m - vm); m = vm; }
+#pragma unroll
+      for (int j = 0; j < VE; ++j) visit(v + j, l[j]);
+    }
+    if constexpr (TOPK) {
+      __syncthreads();
+      const int n = min(n_keys, CAP);
+      // every thread has read n before the next tile appends
+      __syncthreads();
+      if (n > LP_SLACK) thr = lp_compact<NT>(keys, win, &n_keys, n, K);
+    }
+    cur = nxt;
+  }
+  if (ve + tid < V) visit_one(ve + tid, row[ve + tid]);
+
+  // (m, s) and the count across the workgroup
+#pragma unroll
+  for (int off = WAVE / 2; off > 0; off >>= 1) {
+    const float om = __shfl_xor(m, off, WAVE);
+    const float os = __shfl_xor(s, off, WAVE);
+    const float nm = fmaxf(m, om);
+    s = s * __expf(m - nm) + os * __expf(om - nm);
+    m = nm;
+    above += __shfl_xor(above, off, WAVE);
+  }
+  if ((tid & (WAVE - 1)) == 0) {
+    red_m[tid / WAVE] = m;
+    red_s[tid / WAVE] = s;
+    red_c[tid / WAVE] = above;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    for (int w = 1; w < NW; ++w) {
+      const float nm = fmaxf(m, red_m[w]);
+      s = s * __expf(m - nm) + red_s[w] * __expf(red_m[w] - nm);
+      m = nm;
+      above += red_c[w];
+    }
+    const float lse = m + logf(s);
+    sh_lse = lse;
+    lp_out[(long)r * lp_stride] = c - lse;
+    ids_out[(long)r * ids_stride] = tok;
+    rank_out[(long)r * rank_stride] = above + 1;
+  }
+  if constexpr (TOPK) {
+    const int n = min(n_keys, CAP);  // complete: the barrier above follows every append
+    __syncthreads();
+    lp_compact<NT>(keys, win, &n_keys, n, K);
+    if (tid < min(K, n)) {
+      const unsigned long long key = keys[tid];
+      lp_out[(long)r * lp_stride + 1 + tid] = unpack_key_value(key) - sh_lse;
+      ids_out[(long)r * ids_stride + 1 + tid] =
+          (int)(unsigned int)(~(key & 0xffffffffu));
+    }
+  }
+}

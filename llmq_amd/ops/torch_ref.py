@@ -313,6 +313,47 @@ def apply_penalties(
     return l
 
 
+MAX_LOGPROBS = 20
+
+
+def token_logprobs(
+    logits: torch.Tensor,  # [B, vocab] as the lm_head stored them, or fp32
+    tokens: torch.Tensor,  # [B] int: the sampled token of every row
+    k: int,                # alternatives per row, 0..MAX_LOGPROBS
+    softcap: float = 0.0,  # > 0: the model's final soft-cap, still to apply
+    rows: Optional[torch.Tensor] = None,  # [R] int: rows that asked (None = all)
+) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Log-probabilities of the sampled tokens under the model's own
+    distribution: log_softmax of the fp32 logits after the final soft-cap,
+    before penalties, temperature and top-k/top-p/min_p.
+
+    The vocabulary is ordered by (value descending, index ascending), a
+    stable descending sort; torch.topk leaves the order of ties open. Returns
+    for each requested row (ids [R, 1+k] int32, lp [R, 1+k] fp32, rank [R]
+    int32): column 0 is the sampled token, columns 1..k the first k entries
+    of that order, lp = l[id] - logsumexp(l), and rank the 1-based position
+    of the sampled token in the order."""
+    V = logits.size(1)
+    if not 0 <= k <= min(MAX_LOGPROBS, V):
+        raise ValueError(f"k must be in [0, min({MAX_LOGPROBS}, vocab)], got {k}")
+    if rows is not None:
+        rows = rows.long()
+        logits, tokens = logits[rows], tokens[rows]
+    l = logits.float()
+    if softcap > 0:
+        l = torch.tanh(l / softcap) * softcap
+    tok = tokens.long().reshape(-1, 1)
+    ids = tok
+    if k > 0:
+        order = torch.sort(l, dim=-1, descending=True, stable=True).indices
+        ids = torch.cat([tok, order[:, :k]], dim=1)
+    lp = l.gather(1, ids) - torch.logsumexp(l, dim=-1, keepdim=True)
+    c = l.gather(1, tok)
+    idx = torch.arange(V, device=l.device).unsqueeze(0)
+    rank = ((l > c) | ((l == c) & (idx < tok))).sum(dim=-1) + 1
+    return ids.to(torch.int32), lp, rank.to(torch.int32)
+
+
 def sample_tokens(
     logits: torch.Tensor,  # [B, vocab] float
     temperatures: torch.Tensor,  # [B]

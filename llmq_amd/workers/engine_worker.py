@@ -56,6 +56,30 @@ class _FinishedRequest:
     prefill_ms: Optional[float]
     decode_ms: Optional[float]
     cached_tokens: int = 0
+    logprobs: Optional[List[Dict[str, Any]]] = None
+    cumulative_logprob: Optional[float] = None
+
+
+def format_logprobs(entries: List[tuple], tokenizer: Any) -> List[Dict[str, Any]]:
+    """The engine's (token_id, logprob, rank, [(id, logprob)]) entries of one
+    finished request as the Result's list of dicts, with every token id
+    decoded on its own (special tokens kept)."""
+    strings: Dict[int, str] = {}
+
+    def text(tid: int) -> str:
+        if tid not in strings:
+            strings[tid] = tokenizer.decode([tid], skip_special_tokens=False)
+        return strings[tid]
+
+    return [
+        {
+            "token_id": tid, "token": text(tid), "logprob": lp, "rank": rank,
+            "top_logprobs": [
+                {"token_id": i, "token": text(i), "logprob": l} for i, l in top
+            ],
+        }
+        for tid, lp, rank, top in entries
+    ]
 
 
 @dataclass
@@ -195,6 +219,8 @@ class AsyncEngineBridge:
                 steps_since += 1
                 for out in engine.step():
                     if out.finished:
+                        # token strings: decoded here, once per request
+                        entries = getattr(out, "logprobs", None)
                         self._resolve(
                             out.request_id,
                             _FinishedRequest(
@@ -207,6 +233,10 @@ class AsyncEngineBridge:
                                 decode_ms=out.decode_ms,
                                 # engines without a prefix cache report none
                                 cached_tokens=getattr(out, "cached_tokens", 0),
+                                logprobs=None if entries is None else
+                                format_logprobs(entries, engine.tokenizer),
+                                cumulative_logprob=getattr(
+                                    out, "cumulative_logprob", None),
                             ),
                         )
         except BaseException as exc:  # noqa: BLE001 — engine died: fail fast
@@ -423,6 +453,7 @@ class EngineWorker(BaseWorker):
             return default
 
         stop = job.stop if job.stop else stage.get("stop")
+        lp = pick(job.logprobs, "logprobs", None)
         return SamplingParams(
             temperature=float(pick(job.temperature, "temperature", DEFAULT_TEMPERATURE)),
             top_p=float(pick(job.top_p, "top_p", 1.0)),
@@ -437,6 +468,7 @@ class EngineWorker(BaseWorker):
             frequency_penalty=float(
                 pick(job.frequency_penalty, "frequency_penalty", 0.0)),
             min_p=float(pick(job.min_p, "min_p", 0.0)),
+            logprobs=None if lp is None else int(lp),
         )
 
     def _format_prompt(self, job: Job) -> str:
@@ -479,4 +511,6 @@ class EngineWorker(BaseWorker):
             result.queue_wait_ms = stats.queue_wait_ms
             result.prefill_ms = stats.prefill_ms
             result.decode_ms = stats.decode_ms
+            result.logprobs = getattr(stats, "logprobs", None)
+            result.cumulative_logprob = getattr(stats, "cumulative_logprob", None)
         return result
