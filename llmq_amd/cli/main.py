@@ -240,6 +240,9 @@ def worker() -> None:
               help="KV storage dtype; fp8 (OCP e4m3) doubles KV capacity")
 @click.option("--enable-prefix-caching", is_flag=True, default=False,
               help="Reuse the KV of shared prompt heads across jobs")
+@click.option("--quantization", type=click.Choice(["none", "fp8"]), default=None,
+              help="fp8: W8A8 layer projections, quantised at load "
+                   "(halves weight memory); default none or LLMQ_QUANTIZATION")
 @click.option("--engine-overrides", default=None,
               help='JSON dict of EngineConfig overrides, e.g. \'{"enforce_eager": true}\'')
 @click.option("--data-parallel-size", "-dp", type=int, default=None,
@@ -247,8 +250,8 @@ def worker() -> None:
                    "(reference main.py:433-439 passes this to vLLM; here it "
                    "spawns N workers competing on the same queue)")
 def worker_run(model, queue_name, tensor_parallel_size, max_num_seqs, max_model_len,
-               prefetch, kv_cache_dtype, enable_prefix_caching, engine_overrides,
-               data_parallel_size):
+               prefetch, kv_cache_dtype, enable_prefix_caching, quantization,
+               engine_overrides, data_parallel_size):
     """GPU inference worker (in-tree MI355X engine)."""
     import json as _json
 
@@ -259,6 +262,8 @@ def worker_run(model, queue_name, tensor_parallel_size, max_num_seqs, max_model_
         overrides.setdefault("kv_cache_dtype", kv_cache_dtype)
     if enable_prefix_caching:
         overrides.setdefault("enable_prefix_caching", True)
+    if quantization is not None:
+        overrides.setdefault("quantization", quantization)
     if data_parallel_size and data_parallel_size > 1:
         run_engine_worker_dp(
             model, queue_name, data_parallel_size,

@@ -144,6 +144,10 @@ class Config(BaseModel):
         default_factory=lambda: _env_bool("LLMQ_PREFIX_CACHING", False),
         description="Reuse the KV of shared prompt heads across jobs",
     )
+    quantization: str = Field(
+        default_factory=lambda: _env("LLMQ_QUANTIZATION", "none"),
+        description="Weight/activation quantisation of the engine: none | fp8",
+    )
     temperature: float = Field(
         default_factory=lambda: _env_float("LLMQ_TEMPERATURE", 0.7),
         description="Default sampling temperature (reference hardcodes 0.7)",

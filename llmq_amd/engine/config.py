@@ -33,6 +33,30 @@ class EngineConfig:
     # Automatic prefix caching: full KV blocks of finished/running prompts
     # are kept and shared with later prompts that start with the same tokens.
     enable_prefix_caching: bool = False
+    # "none" = weights in the compute dtype; "fp8" = W8A8: the layer
+    # projection weights stored as OCP e4m3 with a per-output-channel scale,
+    # activations quantised per row on the fly, fp8 GEMMs. Opt-in.
+    quantization: str = "none"
+
+    def __post_init__(self) -> None:
+        self._check_quantization()
+
+    def _check_quantization(self) -> None:
+        if self.quantization not in ("none", "fp8"):
+            raise ValueError(
+                f"unknown quantization {self.quantization!r} (expected 'none' or 'fp8')"
+            )
+
+    def resolve_quantization(self, device: torch.device) -> Optional[str]:
+        """None, or "fp8" after checking that the device can run it: the fp8
+        GEMMs need bf16 compute on the GPU; on CPU the fp32 fake-quant
+        reference path runs."""
+        self._check_quantization()
+        if self.quantization == "none":
+            return None
+        if device.type == "cuda" and self.resolve_dtype(device) != torch.bfloat16:
+            raise ValueError("quantization=fp8 requires bf16 execution on GPU")
+        return "fp8"
 
     def resolve_device(self) -> torch.device:
         if self.device == "auto":

@@ -120,7 +120,10 @@ class LLMEngine:
             self.spec.name, self.spec.family, self.spec.param_count() / 1e9,
             self.device, self.dtype, tp,
         )
-        self.model = CausalLM(self.spec, self.device, self.dtype, tp_rank, tp)
+        self.model = CausalLM(
+            self.spec, self.device, self.dtype, tp_rank, tp,
+            quantization=config.resolve_quantization(self.device),
+        )
         self._load_or_init_weights()
         self.tokenizer = load_tokenizer(
             config.model, self.spec.vocab_size, self.spec.bos_token_id, self.spec.eos_token_id

@@ -259,6 +259,11 @@ def spec_from_hf_config(path: Path, name: str) -> ModelSpec:
         raise ValueError(
             f"{name}: Qwen3-MoE ({model_type or arch}) is not supported; "
             "only the dense Qwen3 models are")
+    if cfg.get("quantization_config"):
+        raise ValueError(
+            f"{name}: checkpoints that are already quantised "
+            "(quantization_config in config.json) are not supported; load the "
+            "bf16 checkpoint and set quantization='fp8' to quantise at load")
     if "gemma2" in arch or model_type == "gemma2":
         family = "gemma2"
     elif "qwen3" in arch or model_type == "qwen3":

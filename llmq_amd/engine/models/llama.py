@@ -28,6 +28,7 @@ import torch
 import torch.nn.functional as F
 
 from llmq_amd import ops
+from llmq_amd.ops import torch_ref
 from llmq_amd.engine.forward_meta import DecodeMeta, MixedMeta, PrefillMeta
 from llmq_amd.engine.kv_cache import KVCache
 from llmq_amd.engine.model_specs import ModelSpec
@@ -48,13 +49,24 @@ def _proj(x: torch.Tensor, w: torch.Tensor, bias=None) -> torch.Tensor:
     return F.linear(x, w, bias)
 
 
+# The four projection weights of a layer: the tensors quantization="fp8"
+# stores as float8_e4m3fn [N, K] with an fp32 per-output-channel scale [N]
+# in LayerWeights.<name>_scale.
+LINEARS = ("qkv", "o", "gate_up", "down")
+
+
 class LayerWeights:
     __slots__ = (
         "input_norm", "qkv", "qkv_bias", "q_norm", "k_norm", "o", "post_attn_norm",
         "pre_mlp_norm", "gate_up", "down", "post_mlp_norm",
+        "qkv_scale", "o_scale", "gate_up_scale", "down_scale",
     )
 
     def __init__(self):
+        self.qkv_scale = None
+        self.o_scale = None
+        self.gate_up_scale = None
+        self.down_scale = None
         self.input_norm = None
         self.qkv = None
         self.qkv_bias = None
@@ -76,7 +88,11 @@ class CausalLM:
         dtype: torch.dtype,
         tp_rank: int = 0,
         tp_size: int = 1,
+        quantization: Optional[str] = None,
     ):
+        if quantization not in (None, "fp8"):
+            raise ValueError(f"unknown quantization {quantization!r}")
+        self.fp8 = quantization == "fp8"
         self.spec = spec
         self.device = device
         self.dtype = dtype
@@ -118,22 +134,55 @@ class CausalLM:
     def _empty(self, *shape) -> torch.Tensor:
         return torch.empty(*shape, device=self.device, dtype=self.dtype)
 
+    def linear_shape(self, name: str) -> tuple:
+        """[N, K] of this rank's shard of a layer projection."""
+        h = self.spec.hidden_size
+        return {
+            "qkv": (self.q_size + 2 * self.kv_size, h),
+            "o": (h, self.q_size),
+            "gate_up": (2 * self.inter, h),
+            "down": (h, self.inter),
+        }[name]
+
+    def _empty_linear(self, name: str) -> Optional[torch.Tensor]:
+        # fp8: no storage in the compute dtype; set_linear installs the
+        # quantised tensor, one projection at a time
+        return None if self.fp8 else self._empty(*self.linear_shape(name))
+
+    @torch.no_grad()
+    def set_linear(self, lw: LayerWeights, name: str, src: torch.Tensor) -> None:
+        """Install this rank's shard `src` [N, K] (any dtype or device) as
+        projection `name` of `lw`. Under fp8 it is quantised here, after
+        sharding, so a row-sharded projection gets scales over its local K;
+        the copy in the compute dtype lives only inside this call, and the
+        model never holds two full sets of weights."""
+        if tuple(src.shape) != self.linear_shape(name):
+            raise ValueError(
+                f"shape mismatch: {self.linear_shape(name)} vs {tuple(src.shape)}")
+        if not self.fp8:
+            getattr(lw, name).copy_(src.to(self.dtype))
+            return
+        w = src.to(device=self.device, dtype=torch.bfloat16)
+        w_q, w_scale = torch_ref.quant_fp8_weight(w)
+        setattr(lw, name, w_q)
+        setattr(lw, name + "_scale", w_scale)
+
     def _alloc(self) -> None:
         s = self.spec
         self.embedding = self._empty(s.vocab_size, s.hidden_size)
         for _ in range(s.num_layers):
             lw = LayerWeights()
             lw.input_norm = self._empty(s.hidden_size)
-            lw.qkv = self._empty(self.q_size + 2 * self.kv_size, s.hidden_size)
+            lw.qkv = self._empty_linear("qkv")
             if s.qkv_bias:
                 lw.qkv_bias = self._empty(self.q_size + 2 * self.kv_size)
             if s.qk_norm:
                 lw.q_norm = self._empty(s.head_dim)
                 lw.k_norm = self._empty(s.head_dim)
-            lw.o = self._empty(s.hidden_size, self.q_size)
+            lw.o = self._empty_linear("o")
             lw.pre_mlp_norm = self._empty(s.hidden_size)
-            lw.gate_up = self._empty(2 * self.inter, s.hidden_size)
-            lw.down = self._empty(s.hidden_size, self.inter)
+            lw.gate_up = self._empty_linear("gate_up")
+            lw.down = self._empty_linear("down")
             if s.post_norms:
                 lw.post_attn_norm = self._empty(s.hidden_size)
                 lw.post_mlp_norm = self._empty(s.hidden_size)
@@ -164,22 +213,31 @@ class CausalLM:
                 cpu = torch.randn(t.shape, generator=gen, dtype=torch.float32) * std
                 t.copy_(cpu.to(t.dtype))
 
+        def fill_linear(lw: LayerWeights, name: str, std: float) -> None:
+            if not self.fp8:
+                fill(getattr(lw, name), std)
+                return
+            # the tensor the unquantised model would hold, then its fp8 form
+            w = self._empty(*self.linear_shape(name))
+            fill(w, std)
+            self.set_linear(lw, name, w)
+
         h = self.spec.hidden_size
         std = 0.02
         out_std = std / math.sqrt(2 * self.spec.num_layers)
         fill(self.embedding, std)
         for lw in self.layers:
             lw.input_norm.fill_(1.0 - self.norm_offset)
-            fill(lw.qkv, std)
+            fill_linear(lw, "qkv", std)
             if lw.qkv_bias is not None:
                 lw.qkv_bias.zero_()
             if lw.q_norm is not None:
                 lw.q_norm.fill_(1.0)
                 lw.k_norm.fill_(1.0)
-            fill(lw.o, out_std)
+            fill_linear(lw, "o", out_std)
             lw.pre_mlp_norm.fill_(1.0 - self.norm_offset)
-            fill(lw.gate_up, std)
-            fill(lw.down, out_std)
+            fill_linear(lw, "gate_up", std)
+            fill_linear(lw, "down", out_std)
             if lw.post_attn_norm is not None:
                 lw.post_attn_norm.fill_(1.0 - self.norm_offset)
                 lw.post_mlp_norm.fill_(1.0 - self.norm_offset)
@@ -207,6 +265,9 @@ class CausalLM:
             if lw.post_attn_norm is not None:
                 out[p + "post_attn_norm"] = lw.post_attn_norm
                 out[p + "post_mlp_norm"] = lw.post_mlp_norm
+            if self.fp8:
+                for name in LINEARS:
+                    out[p + name + "_scale"] = getattr(lw, name + "_scale")
         return out
 
     def weight_bytes(self) -> int:
@@ -216,6 +277,36 @@ class CausalLM:
 
     def _norm(self, x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
         return ops.rmsnorm(x, w, self.spec.rms_eps, self.norm_offset)
+
+    # Under fp8 the input of every layer projection travels as a pair
+    # (q [T, K] float8_e4m3fn, scale [T] fp32) from the kernel that produced
+    # it (a fused norm, the gated activation, or quant_fp8_rows after
+    # attention) to the fp8 GEMM; otherwise it is the plain tensor.
+
+    def _linear(self, h, lw: LayerWeights, name: str, bias=None) -> torch.Tensor:
+        w = getattr(lw, name)
+        if self.fp8:
+            return ops.fp8_linear(h[0], h[1], w, getattr(lw, name + "_scale"), bias)
+        return _proj(h, w, bias)
+
+    def _add_norm(self, x, residual, w_post, w, quant: bool):
+        """residual += x (Gemma-2: += norm(x, w_post)); h = norm(residual, w).
+        Returns (h, residual), h quantised when `quant`."""
+        s = self.spec
+        if s.post_norms:
+            # Gemma-2 sandwich fused
+            if quant:
+                q, scale, residual = ops.norm_add_norm_quant_fp8(
+                    x, residual, w_post, w, s.rms_eps, self.norm_offset)
+                return (q, scale), residual
+            return ops.norm_add_norm(
+                x, residual, w_post, w, s.rms_eps, self.norm_offset,
+            )
+        if quant:
+            q, scale, residual = ops.fused_add_rmsnorm_quant_fp8(
+                x, residual, w, s.rms_eps, self.norm_offset)
+            return (q, scale), residual
+        return ops.fused_add_rmsnorm(x, residual, w, s.rms_eps, self.norm_offset)
 
     def _prefill_attn(self, q, k, v, pmeta, kv_cache, layer: int, window: int):
         """Packed varlen attention; chunk continuations assemble their full
@@ -263,12 +354,17 @@ class CausalLM:
             x = x * math.sqrt(s.hidden_size)
             x = x.to(self.dtype)
         residual = x
-        h = self._norm(x, self.layers[0].input_norm)
+        fp8 = self.fp8
+        if fp8:
+            h = ops.rmsnorm_quant_fp8(
+                x, self.layers[0].input_norm, s.rms_eps, self.norm_offset)
+        else:
+            h = self._norm(x, self.layers[0].input_norm)
         n_layers = len(self.layers)
         for i, lw in enumerate(self.layers):
             # ---- attention block (h = normed input, set by the previous
             # block's fused norm — launch count is the decode-step bound)
-            qkv = _proj(h, lw.qkv, lw.qkv_bias)
+            qkv = self._linear(h, lw, "qkv", lw.qkv_bias)
             q, k, v = qkv.split([self.q_size, self.kv_size, self.kv_size], dim=-1)
             T = q.shape[0]
             q = q.view(T, self.heads, s.head_dim)
@@ -305,24 +401,22 @@ class CausalLM:
                     q, kv_cache.k[i], kv_cache.v[i], meta.block_tables,
                     meta.context_lens, s.scale, s.attn_softcap, window,
                 )
-            attn_out = _proj(attn.reshape(T, self.q_size), lw.o)
+            attn = attn.reshape(T, self.q_size)
+            attn_out = self._linear(
+                ops.quant_fp8_rows(attn) if fp8 else attn, lw, "o")
             if tp is not None:
                 attn_out = tp.all_reduce(attn_out)
-            if s.post_norms:
-                # Gemma-2 sandwich fused: residual += norm(attn_out, post);
-                # h = norm(residual, pre_mlp)
-                h, residual = ops.norm_add_norm(
-                    attn_out, residual, lw.post_attn_norm, lw.pre_mlp_norm,
-                    s.rms_eps, self.norm_offset,
-                )
-            else:
-                h, residual = ops.fused_add_rmsnorm(
-                    attn_out, residual, lw.pre_mlp_norm, s.rms_eps, self.norm_offset
-                )
+            # residual += attn_out (Gemma-2: its post norm); h = norm(residual)
+            h, residual = self._add_norm(
+                attn_out, residual, lw.post_attn_norm, lw.pre_mlp_norm, fp8)
             # ---- MLP block
-            gate_up = _proj(h, lw.gate_up)
-            act = ops.gelu_tanh_and_mul(gate_up) if s.gelu else ops.silu_and_mul(gate_up)
-            mlp_out = _proj(act, lw.down)
+            gate_up = self._linear(h, lw, "gate_up")
+            if fp8:
+                act = (ops.gelu_tanh_and_mul_quant_fp8(gate_up) if s.gelu
+                       else ops.silu_and_mul_quant_fp8(gate_up))
+            else:
+                act = ops.gelu_tanh_and_mul(gate_up) if s.gelu else ops.silu_and_mul(gate_up)
+            mlp_out = self._linear(act, lw, "down")
             if tp is not None:
                 mlp_out = tp.all_reduce(mlp_out)
             # The next block's input norm (or the final norm) fuses with this
@@ -330,15 +424,10 @@ class CausalLM:
             w_next = (
                 self.layers[i + 1].input_norm if i + 1 < n_layers else self.final_norm
             )
-            if s.post_norms:
-                h, residual = ops.norm_add_norm(
-                    mlp_out, residual, lw.post_mlp_norm, w_next,
-                    s.rms_eps, self.norm_offset,
-                )
-            else:
-                h, residual = ops.fused_add_rmsnorm(
-                    mlp_out, residual, w_next, s.rms_eps, self.norm_offset
-                )
+            # The last block's output feeds the bf16 lm_head: not quantised.
+            h, residual = self._add_norm(
+                mlp_out, residual, lw.post_mlp_norm, w_next,
+                fp8 and i + 1 < n_layers)
         return h
 
     @torch.no_grad()

@@ -3,7 +3,9 @@
 Reference counterpart: vLLM's weight loader, consumed implicitly through
 AsyncLLMEngine.from_engine_args (vllm_worker.py:105-123). Handles the
 Llama/Qwen2/Qwen3/Gemma-2 HF naming and packs q/k/v and gate/up into the fused
-GEMM tensors. Tensor-parallel loads take each rank's shard only.
+GEMM tensors. Tensor-parallel loads take each rank's shard only. The layer
+projections go through CausalLM.set_linear, which under quantization="fp8"
+quantises each shard as it arrives (per output channel, after sharding).
 """
 
 from __future__ import annotations
@@ -69,7 +71,7 @@ def load_safetensors_weights(model, path: Path) -> None:
         q = _shard_rows(get(p + "self_attn.q_proj.weight"), rank, size)
         k = _shard_rows(get(p + "self_attn.k_proj.weight"), rank, size)
         v = _shard_rows(get(p + "self_attn.v_proj.weight"), rank, size)
-        copy_(lw.qkv, torch.cat([q, k, v], dim=0))
+        model.set_linear(lw, "qkv", torch.cat([q, k, v], dim=0))
         if lw.qkv_bias is not None:
             qb = _shard_rows(get(p + "self_attn.q_proj.bias"), rank, size)
             kb = _shard_rows(get(p + "self_attn.k_proj.bias"), rank, size)
@@ -79,11 +81,11 @@ def load_safetensors_weights(model, path: Path) -> None:
             # per-head-dim, shared by all heads: every TP rank takes them whole
             copy_(lw.q_norm, get(p + "self_attn.q_norm.weight"))
             copy_(lw.k_norm, get(p + "self_attn.k_norm.weight"))
-        copy_(lw.o, _shard_cols(get(p + "self_attn.o_proj.weight"), rank, size))
+        model.set_linear(lw, "o", _shard_cols(get(p + "self_attn.o_proj.weight"), rank, size))
         gate = _shard_rows(get(p + "mlp.gate_proj.weight"), rank, size)
         up = _shard_rows(get(p + "mlp.up_proj.weight"), rank, size)
-        copy_(lw.gate_up, torch.cat([gate, up], dim=0))
-        copy_(lw.down, _shard_cols(get(p + "mlp.down_proj.weight"), rank, size))
+        model.set_linear(lw, "gate_up", torch.cat([gate, up], dim=0))
+        model.set_linear(lw, "down", _shard_cols(get(p + "mlp.down_proj.weight"), rank, size))
         if spec.post_norms:
             copy_(lw.post_attn_norm, get(p + "post_attention_layernorm.weight"))
             copy_(lw.pre_mlp_norm, get(p + "pre_feedforward_layernorm.weight"))

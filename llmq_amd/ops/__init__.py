@@ -106,6 +106,108 @@ def norm_add_norm(
     return torch_ref.norm_add_norm(x, residual, w_post, w_pre, eps, offset)
 
 
+# ---------------------------------------------- fp8 quantisation (W8A8) --
+# Row-wise dynamic activation quantisation under torch_ref.quant_fp8_rows'
+# contract, stand-alone and fused behind each producer of a GEMM input. Every
+# function returns (q [T, K] float8_e4m3fn, scale [T] fp32, ...). On the GPU
+# the inputs are bf16 [T, K]; the fused kernels hold a row in registers, and
+# rows longer than that compose the unfused kernel with quant_fp8_rows (same
+# bits, one more trip through HBM).
+
+_QUANT_NORM_MAX_HIDDEN = 8192    # fused norm kernels (4 vectors per thread)
+_QUANT_ACT_MAX_INTER = 32768     # fused activation kernels (16 vectors)
+
+
+def _quant_out(rows: int, k: int, device) -> Tuple[torch.Tensor, torch.Tensor]:
+    return (torch.empty(rows, k, dtype=torch.float8_e4m3fn, device=device),
+            torch.empty(rows, dtype=torch.float32, device=device))
+
+
+def quant_fp8_rows(x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    if _use_hip(x):
+        q, scale = _quant_out(x.shape[0], x.shape[1], x.device)
+        _EXT.quant_fp8_rows(q, scale, x)
+        return q, scale
+    return torch_ref.quant_fp8_rows(x)
+
+
+def _act_and_mul_quant_fp8(x: torch.Tensor, gelu: bool):
+    d = x.shape[-1] // 2
+    if _use_hip(x) and d <= _QUANT_ACT_MAX_INTER:
+        q, scale = _quant_out(x.shape[0], d, x.device)
+        (_EXT.gelu_tanh_and_mul_quant_fp8 if gelu
+         else _EXT.silu_and_mul_quant_fp8)(q, scale, x)
+        return q, scale
+    return quant_fp8_rows(gelu_tanh_and_mul(x) if gelu else silu_and_mul(x))
+
+
+def silu_and_mul_quant_fp8(x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """quant_fp8_rows(silu_and_mul(x)) without the [T, d] intermediate."""
+    return _act_and_mul_quant_fp8(x, gelu=False)
+
+
+def gelu_tanh_and_mul_quant_fp8(x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """quant_fp8_rows(gelu_tanh_and_mul(x)) without the [T, d] intermediate."""
+    return _act_and_mul_quant_fp8(x, gelu=True)
+
+
+def rmsnorm_quant_fp8(
+    x: torch.Tensor, weight: torch.Tensor, eps: float, offset: float = 0.0
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """quant_fp8_rows(rmsnorm(x, ...)) in one kernel."""
+    if _use_hip(x) and x.shape[-1] <= _QUANT_NORM_MAX_HIDDEN:
+        q, scale = _quant_out(x.shape[0], x.shape[1], x.device)
+        _EXT.rmsnorm_quant_fp8(q, scale, x, weight, eps, offset)
+        return q, scale
+    return quant_fp8_rows(rmsnorm(x, weight, eps, offset))
+
+
+def fused_add_rmsnorm_quant_fp8(
+    x: torch.Tensor, residual: torch.Tensor, weight: torch.Tensor, eps: float,
+    offset: float = 0.0,
+) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """fused_add_rmsnorm with the normed rows quantised: returns (h_q,
+    h_scale, residual). On the GPU residual is updated in place and x is
+    left as it was when the one-kernel form runs."""
+    if _use_hip(x) and x.shape[-1] <= _QUANT_NORM_MAX_HIDDEN:
+        q, scale = _quant_out(x.shape[0], x.shape[1], x.device)
+        _EXT.fused_add_rmsnorm_quant_fp8(q, scale, x, residual, weight, eps, offset)
+        return q, scale, residual
+    h, residual = fused_add_rmsnorm(x, residual, weight, eps, offset)
+    return (*quant_fp8_rows(h), residual)
+
+
+def norm_add_norm_quant_fp8(
+    x: torch.Tensor, residual: torch.Tensor, w_post: torch.Tensor,
+    w_pre: torch.Tensor, eps: float, offset: float = 0.0,
+) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """norm_add_norm (Gemma-2 sandwich) with the normed rows quantised:
+    returns (h_q, h_scale, residual), as fused_add_rmsnorm_quant_fp8."""
+    if _use_hip(x) and x.shape[-1] <= _QUANT_NORM_MAX_HIDDEN:
+        q, scale = _quant_out(x.shape[0], x.shape[1], x.device)
+        _EXT.norm_add_norm_quant_fp8(q, scale, x, residual, w_post, w_pre, eps, offset)
+        return q, scale, residual
+    h, residual = norm_add_norm(x, residual, w_post, w_pre, eps, offset)
+    return (*quant_fp8_rows(h), residual)
+
+
+def fp8_linear(
+    a_q: torch.Tensor,      # [T, K] float8_e4m3fn
+    a_scale: torch.Tensor,  # [T] fp32 per-row scale
+    w_q: torch.Tensor,      # [N, K] float8_e4m3fn (torch linear weight layout)
+    w_scale: torch.Tensor,  # [N] fp32 per-output-channel scale
+    bias: Optional[torch.Tensor] = None,
+) -> torch.Tensor:
+    """(a_q * a_scale[:, None]) @ (w_q * w_scale[:, None]).T + bias. On the
+    GPU the hipBLASLt fp8 GEMM with row-wise scales, bf16 [T, N] out; on CPU
+    the fp32 fake-quant reference."""
+    if not a_q.is_cuda:
+        return torch_ref.fp8_linear(a_q, a_scale, w_q, w_scale, bias)
+    return torch._scaled_mm(
+        a_q, w_q.t(), scale_a=a_scale.unsqueeze(1), scale_b=w_scale.unsqueeze(0),
+        bias=bias, out_dtype=torch.bfloat16)
+
+
 # ----------------------------------------------------------------- rope --
 
 

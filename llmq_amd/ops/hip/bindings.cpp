@@ -168,6 +168,159 @@ void norm_add_norm(at::Tensor x, at::Tensor residual, at::Tensor w_post,
   });
 }
 
+// ------------------------------------------------ fp8 row quantisation --
+
+// Calls f.template operator()<NV>() for the smallest listed NV whose NV
+// vectors per thread (256 threads x 8 elements) cover `hidden`.
+template <int... NVs, typename F>
+void dispatch_row_vecs(int hidden, const char* name, F&& f) {
+  const bool hit = ((hidden <= NVs * 2048 ? (f.template operator()<NVs>(), true)
+                                          : false) || ...);
+  TORCH_CHECK(hit, name, ": row of ", hidden, " exceeds the register form");
+}
+
+// q [rows, hidden] fp8 and scale [rows] fp32 for `rows` bf16 rows.
+void check_quant_out(const at::Tensor& q, const at::Tensor& scale, long rows,
+                     int hidden) {
+  CHECK_GPU(q);
+  CHECK_GPU(scale);
+  TORCH_CHECK(q.scalar_type() == at::kFloat8_e4m3fn && q.is_contiguous() &&
+                  q.numel() == rows * hidden,
+              "q must be contiguous float8_e4m3fn [rows, hidden]");
+  TORCH_CHECK(scale.scalar_type() == at::kFloat && scale.is_contiguous() &&
+                  scale.numel() == rows,
+              "scale must be contiguous float32 [rows]");
+  TORCH_CHECK(hidden % 8 == 0, "row length must be a multiple of 8");
+}
+
+void check_bf16_rows(const at::Tensor& t, const char* what) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kBFloat16 &&
+                  t.is_contiguous() &&
+                  reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0,
+              what, " must be a contiguous, 16-byte aligned bf16 GPU tensor");
+}
+
+auto* fp8_ptr(at::Tensor& q) {
+  return reinterpret_cast<__hip_fp8_e4m3*>(q.data_ptr());
+}
+const bf16_t* bf16_ptr(const at::Tensor& t) {
+  return reinterpret_cast<const bf16_t*>(t.data_ptr());
+}
+
+constexpr int kQuantRegsMax = 16 * 2048;  // longest row quant.hip holds in registers
+constexpr int kNormQuantMax = 4 * 2048;   // same for the fused norms
+
+void quant_fp8_rows(at::Tensor q, at::Tensor scale, at::Tensor x) {
+  TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16 && x.dim() == 2 &&
+                  x.stride(1) == 1 && x.stride(0) % 8 == 0 &&
+                  reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0,
+              "x must be a 16-byte aligned bf16 [T, K] GPU tensor with unit "
+              "inner stride and a row stride that is a multiple of 8");
+  const int hidden = x.size(1);
+  const long rows = x.size(0);
+  check_quant_out(q, scale, rows, hidden);
+  if (rows == 0) return;
+  if (hidden > kQuantRegsMax) {
+    hipLaunchKernelGGL(quant_fp8_rows_long_kernel, dim3(rows), dim3(256), 0,
+                       stream(), fp8_ptr(q), scale.data_ptr<float>(),
+                       bf16_ptr(x), hidden, (long)x.stride(0));
+    return;
+  }
+  dispatch_row_vecs<1, 2, 4, 8, 16>(hidden, "quant_fp8_rows", [&]<int NV>() {
+    hipLaunchKernelGGL(quant_fp8_rows_kernel<NV>, dim3(rows), dim3(256), 0,
+                       stream(), fp8_ptr(q), scale.data_ptr<float>(),
+                       bf16_ptr(x), hidden, (long)x.stride(0));
+  });
+}
+
+template <bool GELU>
+void act_and_mul_quant(at::Tensor q, at::Tensor scale, at::Tensor in) {
+  check_bf16_rows(in, "gate_up");
+  TORCH_CHECK(in.dim() == 2 && in.size(1) % 2 == 0, "gate_up must be [T, 2*d]");
+  const int d = in.size(1) / 2;
+  const long rows = in.size(0);
+  check_quant_out(q, scale, rows, d);
+  if (rows == 0) return;
+  dispatch_row_vecs<1, 2, 4, 8, 16>(d, "act_and_mul_quant_fp8", [&]<int NV>() {
+    hipLaunchKernelGGL((act_and_mul_quant_kernel<GELU, NV>), dim3(rows),
+                       dim3(256), 0, stream(), fp8_ptr(q),
+                       scale.data_ptr<float>(), bf16_ptr(in), d);
+  });
+}
+
+void silu_and_mul_quant_fp8(at::Tensor q, at::Tensor scale, at::Tensor in) {
+  act_and_mul_quant<false>(q, scale, in);
+}
+void gelu_tanh_and_mul_quant_fp8(at::Tensor q, at::Tensor scale, at::Tensor in) {
+  act_and_mul_quant<true>(q, scale, in);
+}
+
+void check_norm_weight(const at::Tensor& w, int hidden) {
+  check_bf16_rows(w, "norm weight");
+  TORCH_CHECK(w.numel() == hidden, "norm weight must have `hidden` elements");
+}
+
+void rmsnorm_quant_fp8(at::Tensor q, at::Tensor scale, at::Tensor x,
+                       at::Tensor weight, double eps, double offset) {
+  check_bf16_rows(x, "x");
+  TORCH_CHECK(x.dim() == 2, "x must be [T, hidden]");
+  const int hidden = x.size(1);
+  const long rows = x.size(0);
+  check_quant_out(q, scale, rows, hidden);
+  check_norm_weight(weight, hidden);
+  if (rows == 0) return;
+  dispatch_row_vecs<1, 2, 4>(hidden, "rmsnorm_quant_fp8", [&]<int NV>() {
+    hipLaunchKernelGGL(rmsnorm_quant_kernel<NV>, dim3(rows), dim3(256), 0,
+                       stream(), fp8_ptr(q), scale.data_ptr<float>(),
+                       bf16_ptr(x), bf16_ptr(weight), hidden, (float)eps,
+                       (float)offset);
+  });
+}
+
+void fused_add_rmsnorm_quant_fp8(at::Tensor q, at::Tensor scale, at::Tensor x,
+                                 at::Tensor residual, at::Tensor weight,
+                                 double eps, double offset) {
+  check_bf16_rows(x, "x");
+  check_bf16_rows(residual, "residual");
+  TORCH_CHECK(x.dim() == 2 && residual.sizes() == x.sizes(),
+              "x and residual must both be [T, hidden]");
+  const int hidden = x.size(1);
+  const long rows = x.size(0);
+  check_quant_out(q, scale, rows, hidden);
+  check_norm_weight(weight, hidden);
+  if (rows == 0) return;
+  dispatch_row_vecs<1, 2, 4>(hidden, "fused_add_rmsnorm_quant_fp8", [&]<int NV>() {
+    hipLaunchKernelGGL(fused_add_rmsnorm_quant_kernel<NV>, dim3(rows),
+                       dim3(256), 0, stream(), fp8_ptr(q),
+                       scale.data_ptr<float>(), bf16_ptr(x),
+                       reinterpret_cast<bf16_t*>(residual.data_ptr()),
+                       bf16_ptr(weight), hidden, (float)eps, (float)offset);
+  });
+}
+
+void norm_add_norm_quant_fp8(at::Tensor q, at::Tensor scale, at::Tensor x,
+                             at::Tensor residual, at::Tensor w_post,
+                             at::Tensor w_pre, double eps, double offset) {
+  check_bf16_rows(x, "x");
+  check_bf16_rows(residual, "residual");
+  TORCH_CHECK(x.dim() == 2 && residual.sizes() == x.sizes(),
+              "x and residual must both be [T, hidden]");
+  const int hidden = x.size(1);
+  const long rows = x.size(0);
+  check_quant_out(q, scale, rows, hidden);
+  check_norm_weight(w_post, hidden);
+  check_norm_weight(w_pre, hidden);
+  if (rows == 0) return;
+  dispatch_row_vecs<1, 2, 4>(hidden, "norm_add_norm_quant_fp8", [&]<int NV>() {
+    hipLaunchKernelGGL(norm_add_norm_quant_kernel<NV>, dim3(rows), dim3(256),
+                       0, stream(), fp8_ptr(q), scale.data_ptr<float>(),
+                       bf16_ptr(x),
+                       reinterpret_cast<bf16_t*>(residual.data_ptr()),
+                       bf16_ptr(w_post), bf16_ptr(w_pre), hidden, (float)eps,
+                       (float)offset);
+  });
+}
+
 // ------------------------------------------------------------- KV cache --
 
 void reshape_and_cache(at::Tensor key, at::Tensor value, at::Tensor k_cache,
@@ -988,6 +1141,12 @@ TORCH_LIBRARY(llmq_amd, m) {
   m.def("topk_topp_bound(Tensor(a!) out_bound, Tensor logits, Tensor temps, Tensor top_ps, Tensor top_ks, float softcap=0.0, Tensor? min_ps=None, Tensor? pen_table=None, Tensor? pen_slots=None, Tensor? pen_params=None) -> ()");
   m.def("penalty_count_tokens(Tensor(a!) table, Tensor slots, Tensor tokens) -> ()");
   m.def("skinny_gemm(Tensor(a!) out, Tensor x, Tensor w, Tensor? bias, int splitk) -> ()");
+  m.def("quant_fp8_rows(Tensor(a!) q, Tensor(b!) scale, Tensor x) -> ()");
+  m.def("silu_and_mul_quant_fp8(Tensor(a!) q, Tensor(b!) scale, Tensor gate_up) -> ()");
+  m.def("gelu_tanh_and_mul_quant_fp8(Tensor(a!) q, Tensor(b!) scale, Tensor gate_up) -> ()");
+  m.def("rmsnorm_quant_fp8(Tensor(a!) q, Tensor(b!) scale, Tensor x, Tensor weight, float eps, float offset) -> ()");
+  m.def("fused_add_rmsnorm_quant_fp8(Tensor(a!) q, Tensor(b!) scale, Tensor x, Tensor(c!) residual, Tensor weight, float eps, float offset) -> ()");
+  m.def("norm_add_norm_quant_fp8(Tensor(a!) q, Tensor(b!) scale, Tensor x, Tensor(c!) residual, Tensor w_post, Tensor w_pre, float eps, float offset) -> ()");
   m.def("norm_add_norm(Tensor(a!) x, Tensor(b!) residual, Tensor w_post, Tensor w_pre, float eps, float offset) -> ()");
   m.def("rope_and_cache(Tensor(a!) q, Tensor(b!) k, Tensor value, Tensor(c!) k_cache, Tensor(d!) v_cache, Tensor positions, Tensor cos_sin, Tensor slot_mapping) -> ()");
   m.def("qknorm_rope_and_cache(Tensor(a!) q, Tensor(b!) k, Tensor value, Tensor(c!) k_cache, Tensor(d!) v_cache, Tensor q_weight, Tensor k_weight, float eps, float offset, Tensor positions, Tensor cos_sin, Tensor slot_mapping) -> ()");
@@ -1009,6 +1168,12 @@ TORCH_LIBRARY_IMPL(llmq_amd, CUDA, m) {
   m.impl("token_logprobs", &token_logprobs);
   m.impl("skinny_gemm", &skinny_gemm);
   m.impl("norm_add_norm", &norm_add_norm);
+  m.impl("quant_fp8_rows", &quant_fp8_rows);
+  m.impl("silu_and_mul_quant_fp8", &silu_and_mul_quant_fp8);
+  m.impl("gelu_tanh_and_mul_quant_fp8", &gelu_tanh_and_mul_quant_fp8);
+  m.impl("rmsnorm_quant_fp8", &rmsnorm_quant_fp8);
+  m.impl("fused_add_rmsnorm_quant_fp8", &fused_add_rmsnorm_quant_fp8);
+  m.impl("norm_add_norm_quant_fp8", &norm_add_norm_quant_fp8);
   m.impl("rope_and_cache", &rope_and_cache);
   m.impl("qknorm_rope_and_cache", &qknorm_rope_and_cache);
   m.impl("gather_paged_kv", &gather_paged_kv);

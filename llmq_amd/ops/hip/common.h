@@ -119,4 +119,31 @@ DEVINL float block_reduce_sum(float x, float* scratch) {
   return r;
 }
 
+// Same protocol for a maximum of non-negative values.
+DEVINL float block_reduce_max(float x, float* scratch) {
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int wid = threadIdx.x / WAVE;
+  x = wave_reduce_max(x);
+  if (lane == 0) scratch[wid] = x;
+  __syncthreads();
+  const int nw = blockDim.x / WAVE;
+  float r = (threadIdx.x < nw) ? scratch[threadIdx.x] : 0.0f;
+  if (wid == 0) {
+    r = wave_reduce_max(r);
+    if (lane == 0) scratch[0] = r;
+  }
+  __syncthreads();
+  r = scratch[0];
+  __syncthreads();
+  return r;
+}
+
+// ---- packed fp8 (OCP e4m3fn) conversion -----------------------------------
+// Four floats -> four fp8 bytes (a in byte 0) with the native packed convert
+// from_f32<__hip_fp8_e4m3> wraps: two VOPs per word, RNE.
+DEVINL int pack4_fp8(float a, float b, float c, float d) {
+  int w = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, 0, false);
+  return __builtin_amdgcn_cvt_pk_fp8_f32(c, d, w, true);
+}
+
 DEVINL int ceil_div(int a, int b) { return (a + b - 1) / b; }

@@ -7,6 +7,30 @@
 
 #include "common.h"
 
+// Element helpers shared with the fp8-quantising forms in quant.hip: one
+// definition of each rounding-sensitive expression, so the fused kernels
+// produce the bits of the kernels below.
+
+// One normalised element before rounding to T.
+DEVINL float norm_elem(float v, float inv, float w, float offset) {
+  return v * inv * (w + offset);
+}
+
+// act(gate) * up before rounding to T.
+template <bool GELU>
+DEVINL float act_mul_elem(float g, float u) {
+  float act;
+  if (GELU) {
+    // tanh-approx GELU (HF "gelu_pytorch_tanh")
+    const float c = 0.7978845608028654f;  // sqrt(2/pi)
+    float inner = c * (g + 0.044715f * g * g * g);
+    act = 0.5f * g * (1.0f + tanhf(inner));
+  } else {
+    act = g / (1.0f + __expf(-g));  // SiLU
+  }
+  return act * u;
+}
+
 // ---------------------------------------------------------------- RMSNorm --
 // One workgroup per row. 256 threads, each handling 16B chunks grid-stride.
 // `offset` = 1.0 for Gemma's (1 + w) convention.
@@ -39,7 +63,7 @@ __global__ void rmsnorm_kernel(T* __restrict__ out, const T* __restrict__ in,
     Vec8<T> r;
 #pragma unroll
     for (int j = 0; j < VE; ++j)
-      r.data[j] = from_f32<T>(to_f32(v.data[j]) * inv * (to_f32(w.data[j]) + offset));
+      r.data[j] = from_f32<T>(norm_elem(to_f32(v.data[j]), inv, to_f32(w.data[j]), offset));
     store16(o + i, r);
   }
 }
@@ -78,7 +102,7 @@ __global__ void fused_add_rmsnorm_kernel(T* __restrict__ x, T* __restrict__ resi
     Vec8<T> r;
 #pragma unroll
     for (int j = 0; j < VE; ++j)
-      r.data[j] = from_f32<T>(to_f32(v.data[j]) * inv * (to_f32(w.data[j]) + offset));
+      r.data[j] = from_f32<T>(norm_elem(to_f32(v.data[j]), inv, to_f32(w.data[j]), offset));
     store16(xr + i, r);
   }
 }
@@ -100,17 +124,8 @@ __global__ void act_and_mul_kernel(T* __restrict__ out, const T* __restrict__ in
     Vec8<T> r;
 #pragma unroll
     for (int j = 0; j < VE; ++j) {
-      float g = to_f32(a.data[j]);
-      float act;
-      if (GELU) {
-        // tanh-approx GELU (HF "gelu_pytorch_tanh")
-        const float c = 0.7978845608028654f;  // sqrt(2/pi)
-        float inner = c * (g + 0.044715f * g * g * g);
-        act = 0.5f * g * (1.0f + tanhf(inner));
-      } else {
-        act = g / (1.0f + __expf(-g));  // SiLU
-      }
-      r.data[j] = from_f32<T>(act * to_f32(b.data[j]));
+      r.data[j] = from_f32<T>(
+          act_mul_elem<GELU>(to_f32(a.data[j]), to_f32(b.data[j])));
     }
     store16(out + row * d + col, r);
   }
@@ -183,7 +198,7 @@ __global__ void norm_add_norm_kernel(T* __restrict__ x, T* __restrict__ residual
     Vec8<T> nr;
 #pragma unroll
     for (int j = 0; j < VE; ++j) {
-      const float t = to_f32(vx.data[j]) * inv1 * (to_f32(vw.data[j]) + offset);
+      const float t = norm_elem(to_f32(vx.data[j]), inv1, to_f32(vw.data[j]), offset);
       const float r = to_f32(vr.data[j]) + t;
       nr.data[j] = from_f32<T>(r);
       ss2 += r * r;
@@ -199,7 +214,7 @@ __global__ void norm_add_norm_kernel(T* __restrict__ x, T* __restrict__ residual
     Vec8<T> o;
 #pragma unroll
     for (int j = 0; j < VE; ++j)
-      o.data[j] = from_f32<T>(to_f32(vr.data[j]) * inv2 * (to_f32(vw.data[j]) + offset));
+      o.data[j] = from_f32<T>(norm_elem(to_f32(vr.data[j]), inv2, to_f32(vw.data[j]), offset));
     store16(xr + i, o);
   }
 }
@@ -212,16 +227,16 @@ __global__ void norm_add_norm_kernel(T* __restrict__ x, T* __restrict__ residual
 // (i = tid*8 + k*256*8), per-thread summation order and both reductions are
 // those of norm_add_norm_kernel, so the outputs are bitwise the same.
 // Launch with 256 threads.
+// The row body returns the normed row in `o` (vector k of this thread at
+// i = tid*8 + k*256*8) so that norm_add_norm_quant_kernel (quant.hip) can
+// quantise the same values instead of storing them.
 template <typename T, int NV>
-__global__ __launch_bounds__(256) void norm_add_norm_regs_kernel(
-    T* __restrict__ x, T* __restrict__ residual, const T* __restrict__ w_post,
-    const T* __restrict__ w_pre, int hidden, float eps, float offset) {
+DEVINL void norm_add_norm_regs_row(const T* __restrict__ xr, T* __restrict__ rr,
+                                   const T* __restrict__ w_post,
+                                   const T* __restrict__ w_pre, int hidden,
+                                   float eps, float offset, float* red,
+                                   Vec8<T> (&o)[NV]) {
   constexpr int VE = Vec8<T>::kElems;
-  __shared__ float red[4];
-  const int row = blockIdx.x;
-  T* xr = x + (long)row * hidden;
-  T* rr = residual + (long)row * hidden;
-
   Vec8<T> vx[NV], vr[NV], vwp[NV], vwn[NV];
 #pragma unroll
   for (int k = 0; k < NV; ++k) {
@@ -257,7 +272,7 @@ __global__ __launch_bounds__(256) void norm_add_norm_regs_kernel(
     if (i < hidden) {
 #pragma unroll
       for (int j = 0; j < VE; ++j) {
-        const float t = to_f32(vx[k].data[j]) * inv1 * (to_f32(vwp[k].data[j]) + offset);
+        const float t = norm_elem(to_f32(vx[k].data[j]), inv1, to_f32(vwp[k].data[j]), offset);
         const float r = to_f32(vr[k].data[j]) + t;
         vr[k].data[j] = from_f32<T>(r);
         ss2 += r * r;
@@ -272,11 +287,27 @@ __global__ __launch_bounds__(256) void norm_add_norm_regs_kernel(
   for (int k = 0; k < NV; ++k) {
     const int i = threadIdx.x * VE + k * 256 * VE;
     if (i < hidden) {
-      Vec8<T> o;
 #pragma unroll
       for (int j = 0; j < VE; ++j)
-        o.data[j] = from_f32<T>(to_f32(vr[k].data[j]) * inv2 * (to_f32(vwn[k].data[j]) + offset));
-      store16(xr + i, o);
+        o[k].data[j] = from_f32<T>(norm_elem(to_f32(vr[k].data[j]), inv2, to_f32(vwn[k].data[j]), offset));
     }
+  }
+}
+
+template <typename T, int NV>
+__global__ __launch_bounds__(256) void norm_add_norm_regs_kernel(
+    T* __restrict__ x, T* __restrict__ residual, const T* __restrict__ w_post,
+    const T* __restrict__ w_pre, int hidden, float eps, float offset) {
+  constexpr int VE = Vec8<T>::kElems;
+  __shared__ float red[4];
+  const int row = blockIdx.x;
+  T* xr = x + (long)row * hidden;
+  Vec8<T> o[NV];
+  norm_add_norm_regs_row<T, NV>(xr, residual + (long)row * hidden, w_post,
+                                w_pre, hidden, eps, offset, red, o);
+#pragma unroll
+  for (int k = 0; k < NV; ++k) {
+    const int i = threadIdx.x * VE + k * 256 * VE;
+    if (i < hidden) store16(xr + i, o[k]);
   }
 }

@@ -1,6 +1,7 @@
 // Umbrella translation unit: all kernels + torch bindings compiled together
 // (template instantiation happens at the launch sites in bindings.cpp).
 #include "elementwise.hip"
+#include "quant.hip"
 #include "kvcache.hip"
 #include "prefill_attention.hip"
 #include "decode_attention.hip"

@@ -112,6 +112,41 @@ def gelu_tanh_and_mul(x: torch.Tensor) -> torch.Tensor:
     return (torch.nn.functional.gelu(a.float(), approximate="tanh") * b.float()).to(x.dtype)
 
 
+FP8_MAX = 448.0  # largest finite float8_e4m3fn
+
+
+def quant_fp8_rows(x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Row-wise dynamic fp8 quantisation, the contract of the HIP quant
+    kernels: a = max(amax |x|, 1e-30), scale = a / 448, q = e4m3fn(clamp(x *
+    (448 / a), ±448)), all in fp32 with true divisions (tensor divisors: a
+    Python-scalar divisor may become a multiply by its reciprocal).
+    x [..., K] → (q [..., K] float8_e4m3fn, scale [...] fp32)."""
+    xf = x.float()
+    a = xf.abs().amax(dim=-1).clamp_min(1e-30)
+    top = torch.full_like(a, FP8_MAX)
+    q = (xf * (top / a).unsqueeze(-1)).clamp(-FP8_MAX, FP8_MAX)
+    return q.to(torch.float8_e4m3fn), a / top
+
+
+def quant_fp8_weight(w: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Per-output-channel fp8 weight [N, K] + fp32 scale [N] of the bf16
+    rounding of w: what a bf16 engine would have held, whatever dtype and
+    device w is in, so CPU and GPU engines quantise the same values."""
+    return quant_fp8_rows(w.to(torch.bfloat16))
+
+
+def fp8_linear(
+    a_q: torch.Tensor, a_scale: torch.Tensor, w_q: torch.Tensor,
+    w_scale: torch.Tensor, bias: Optional[torch.Tensor] = None,
+) -> torch.Tensor:
+    """Fake-quant reference of the W8A8 GEMM: dequantise both operands to
+    fp32, fp32 matmul, add the bias. Returns fp32 [T, N]."""
+    a = a_q.float() * a_scale.unsqueeze(-1)
+    w = w_q.float() * w_scale.unsqueeze(-1)
+    out = a @ w.t()
+    return out if bias is None else out + bias.float()
+
+
 def reshape_and_cache(
     key: torch.Tensor,  # [T, kv_heads, head_dim]
     value: torch.Tensor,

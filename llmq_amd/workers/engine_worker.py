@@ -386,6 +386,10 @@ class EngineWorker(BaseWorker):
             kwargs["max_model_len"] = max_len
         if self.config.enable_prefix_caching:
             kwargs["enable_prefix_caching"] = True
+        # a pipeline stage's own setting wins over the environment's
+        quantization = self.stage_config.get("quantization", self.config.quantization)
+        if quantization != "none":
+            kwargs["quantization"] = str(quantization)
         kwargs.update(self.engine_overrides)
         return kwargs
 
