@@ -144,6 +144,11 @@ class Config(BaseModel):
         default_factory=lambda: _env_bool("LLMQ_PREFIX_CACHING", False),
         description="Reuse the KV of shared prompt heads across jobs",
     )
+    shared_prefix_decode: bool = Field(
+        default_factory=lambda: _env_bool("LLMQ_SHARED_PREFIX_DECODE", False),
+        description="Attend the prompt head shared by a decode batch once "
+                    "(cascade attention); needs prefix caching",
+    )
     quantization: str = Field(
         default_factory=lambda: _env("LLMQ_QUANTIZATION", "none"),
         description="Weight/activation quantisation of the engine: none | fp8",

@@ -33,6 +33,11 @@ class EngineConfig:
     # Automatic prefix caching: full KV blocks of finished/running prompts
     # are kept and shared with later prompts that start with the same tokens.
     enable_prefix_caching: bool = False
+    # Cascade decode attention for batches that share a prompt prefix: the
+    # blocks common to every sequence of a decode step are attended once per
+    # 128 query rows instead of once per sequence. Needs prefix caching (that
+    # is what makes the blocks common). Opt-in.
+    shared_prefix_decode: bool = False
     # "none" = weights in the compute dtype; "fp8" = W8A8: the layer
     # projection weights stored as OCP e4m3 with a per-output-channel scale,
     # activations quantised per row on the fly, fp8 GEMMs. Opt-in.
@@ -40,6 +45,8 @@ class EngineConfig:
 
     def __post_init__(self) -> None:
         self._check_quantization()
+        if self.shared_prefix_decode and not self.enable_prefix_caching:
+            raise ValueError("shared_prefix_decode requires enable_prefix_caching")
 
     def _check_quantization(self) -> None:
         if self.quantization not in ("none", "fp8"):

@@ -51,6 +51,12 @@ class DecodeMeta:
     block_tables: torch.Tensor  # [B, max_blocks] int32
     context_lens: torch.Tensor  # [B] int32 (including the new token)
     slot_mapping: torch.Tensor  # [B] int64
+    # Shared-prefix decode (None = plain decode attention). When set, the
+    # leading prefix_len tokens of EVERY row live in the blocks of
+    # prefix_table, and block_tables / context_lens above describe only what
+    # follows them (each row's own blocks, >= 1 token).
+    prefix_table: "torch.Tensor | None" = None  # [Wp] int32
+    prefix_len: "torch.Tensor | None" = None    # [1] int32, on the device
 
     is_prefill: bool = False
     is_mixed: bool = False

@@ -108,8 +108,44 @@ class ModelRunner:
         # index_copy_, per-token index lists) for A/B and bisection.
         self.paged_gather = os.environ.get(
             "LLMQ_PAGED_GATHER", "1") not in ("0", "false", "")
+        self.shared_prefix = self._shared_prefix_active()
         if self.use_graphs:
             self._alloc_static_buffers()
+
+    # -- shared-prefix decode ---------------------------------------------
+
+    def _shared_prefix_active(self) -> bool:
+        """shared_prefix_decode, if the HIP cascade kernels can serve this
+        model and cache (the CPU runs the reference composition)."""
+        if not self.config.shared_prefix_decode:
+            return False
+        if self.device.type != "cuda":
+            return True
+        m = self.model
+        ok = ops.shared_prefix_kernel_supported(
+            m.dtype, self.kv_cache.k[0].dtype, m.spec.head_dim,
+            m.heads // m.kv_heads, self.block_size, self.max_blocks_per_seq,
+            self.max_blocks_per_seq)
+        if not ok:
+            logger.warning(
+                "shared_prefix_decode is off: the cascade kernels need a bf16 "
+                "model and KV cache, head_dim 128/256, GQA group <= 16 and at "
+                "most %d blocks per sequence", ops.SHARED_PREFIX_MAX_BT)
+        return ok
+
+    def _shared_prefix_blocks(self, seqs: List[Sequence], ctx: List[int]) -> int:
+        """Leading physical blocks that every sequence of this decode step
+        shares. Capped so that each sequence keeps at least one token of its
+        own (the block being written is never in the prefix); 0 unless the
+        prefix fills at least one 128-token stretch."""
+        bs = self.block_size
+        n = min((c - 1) // bs for c in ctx)
+        if n * bs < 128 or len(seqs) < 2:  # a lone sequence shares with nobody
+            return 0
+        heads = np.array([s.block_table[:n] for s in seqs], dtype=np.int32)
+        differ = (heads != heads[0]).any(axis=0)
+        p = int(differ.argmax()) if differ.any() else n
+        return p if p * bs >= 128 else 0
 
     # -- static buffers / graph capture ---------------------------------
 
@@ -143,6 +179,17 @@ class ModelRunner:
         # the old sequence's block ids. num_preemptions guards the same-life
         # case where preemption-by-recompute reassigns the whole table.
         self._staged_rows: List[Tuple[int, int, int]] = [(-1, -1, 0)] * B
+        # Shared-prefix decode: in_block_tables then holds each row's blocks
+        # BEHIND the shared ones (so the staging key gains the prefix block
+        # count), in_context_lens the tokens behind them.
+        self._staged_prefix = 0
+        if self.shared_prefix:
+            self.in_prefix_table = torch.zeros(
+                self.max_blocks_per_seq, dtype=torch.int32, device=dev)
+            self.in_prefix_len = torch.zeros(1, dtype=torch.int32, device=dev)
+            self.h_prefix_table = torch.zeros(
+                self.max_blocks_per_seq, dtype=torch.int32, pin_memory=True)
+            self.h_prefix_len = torch.zeros(1, dtype=torch.int32, pin_memory=True)
 
     def capture_graphs(self) -> None:
         """Capture the decode forward for each batch-size bucket."""
@@ -156,6 +203,9 @@ class ModelRunner:
                 context_lens=self.in_context_lens[:bs],
                 slot_mapping=self.in_slots[:bs],
             )
+            if self.shared_prefix:  # captured with the cascade op (prefix 0)
+                meta.prefix_table = self.in_prefix_table
+                meta.prefix_len = self.in_prefix_len
             # warmup (also materialises workspace allocations)
             out = self.model.forward(self.in_ids[:bs], self.in_pos[:bs], self.kv_cache, meta)
             torch.cuda.synchronize()
@@ -350,18 +400,26 @@ class ModelRunner:
         if bucket is not None and bucket in self._graphs:
             return self._decode_with_graph(seqs, bucket, ids, pos, slots, ctx)
 
+        # shared-prefix decode: the first P blocks go to the prefix table, the
+        # rows keep what follows (P == 0: the plain tables, an empty prefix)
+        P = self._shared_prefix_blocks(seqs, ctx) if self.shared_prefix else 0
         block_tables = torch.zeros(
-            B, max(len(s.block_table) for s in seqs), dtype=torch.int32, device=dev
+            B, max(len(s.block_table) for s in seqs) - P, dtype=torch.int32, device=dev
         )
         bt_np = np.zeros(tuple(block_tables.shape), dtype=np.int32)
         for i, s in enumerate(seqs):
-            bt_np[i, : len(s.block_table)] = s.block_table
+            bt_np[i, : len(s.block_table) - P] = s.block_table[P:]
         block_tables.copy_(torch.from_numpy(bt_np))
         meta = DecodeMeta(
             block_tables=block_tables,
-            context_lens=torch.tensor(ctx, dtype=torch.int32, device=dev),
+            context_lens=torch.tensor(
+                [c - P * bs for c in ctx], dtype=torch.int32, device=dev),
             slot_mapping=torch.tensor(slots, dtype=torch.long, device=dev),
         )
+        if self.shared_prefix:
+            meta.prefix_table = torch.tensor(
+                seqs[0].block_table[:P] or [0], dtype=torch.int32, device=dev)
+            meta.prefix_len = torch.tensor([P * bs], dtype=torch.int32, device=dev)
         input_ids = torch.tensor(ids, dtype=torch.long, device=dev)
         positions = torch.tensor(pos, dtype=torch.long, device=dev)
         hidden = self.model.forward(input_ids, positions, self.kv_cache, meta)
@@ -376,6 +434,15 @@ class ModelRunner:
         self.h_ids[:B] = torch.tensor(ids, dtype=torch.long)
         self.h_pos[:B] = torch.tensor(pos, dtype=torch.long)
         self.h_slots[:B] = torch.tensor(slots, dtype=torch.long)
+        P = self._shared_prefix_blocks(seqs, ctx) if self.shared_prefix else 0
+        if self.shared_prefix:
+            self.h_prefix_table[:P] = torch.tensor(
+                seqs[0].block_table[:P], dtype=torch.int32)
+            self.h_prefix_len[0] = P * self.block_size
+            if P != self._staged_prefix:  # every row's own blocks moved
+                self._staged_rows = [(-2, -2, 0)] * len(self._staged_rows)
+                self._staged_prefix = P
+            ctx = [c - P * self.block_size for c in ctx]
         self.h_context_lens[:B] = torch.tensor(ctx, dtype=torch.int32)
         self.h_context_lens[B:bucket] = 1
         # Block tables are staged INCREMENTALLY: a row is rewritten only when
@@ -386,11 +453,11 @@ class ModelRunner:
         bt_np = self.h_block_tables.numpy()
         max_w = 1
         for i, s in enumerate(seqs):
-            n = len(s.block_table)
+            n = len(s.block_table) - P
             if n > max_w:
                 max_w = n
             if self._staged_rows[i] != (s.uid, s.num_preemptions, n):
-                bt_np[i, :n] = s.block_table
+                bt_np[i, :n] = s.block_table[P:] if P else s.block_table
                 self._staged_rows[i] = (s.uid, s.num_preemptions, n)
         if B < bucket:
             # pad rows: context_len 1 pointing at block 0 (defined garbage,
@@ -409,6 +476,10 @@ class ModelRunner:
         self.in_block_tables[:bucket, :max_w].copy_(
             self.h_block_tables[:bucket, :max_w], non_blocking=True
         )
+        if self.shared_prefix:
+            self.in_prefix_table[: max(P, 1)].copy_(
+                self.h_prefix_table[: max(P, 1)], non_blocking=True)
+            self.in_prefix_len.copy_(self.h_prefix_len, non_blocking=True)
         self._graphs[bucket].replay()
         logits, cap = self._logits_for_sampling(self.out_hidden[:B])
         return self._sample(logits, seqs, softcap=cap)

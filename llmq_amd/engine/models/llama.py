@@ -396,6 +396,12 @@ class CausalLM:
                     q[nd:], k[nd:], v[nd:], meta.prefill, kv_cache, i, window
                 )
                 attn = torch.cat([attn_d, attn_p], dim=0)
+            elif meta.prefix_table is not None:
+                attn = ops.shared_prefix_decode_attention(
+                    q, kv_cache.k[i], kv_cache.v[i], meta.prefix_table,
+                    meta.prefix_len, meta.block_tables, meta.context_lens,
+                    s.scale, s.attn_softcap, window,
+                )
             else:
                 attn = ops.paged_decode_attention(
                     q, kv_cache.k[i], kv_cache.v[i], meta.block_tables,

@@ -359,6 +359,76 @@ def paged_decode_attention(
     )
 
 
+SHARED_PREFIX_MAX_BT = 1024  # table entries the cascade kernels stage in LDS
+
+
+def shared_prefix_kernel_supported(
+    dtype: torch.dtype, cache_dtype: torch.dtype, head_dim: int, group: int,
+    block_size: int, prefix_blocks: int, suffix_blocks: int,
+) -> bool:
+    """The envelope of the HIP cascade kernels (bf16 q and KV cache)."""
+    return (
+        dtype == torch.bfloat16 and cache_dtype == torch.bfloat16
+        and head_dim in (128, 256) and 1 <= group <= 16
+        and block_size in (16, 32)
+        and 1 <= prefix_blocks <= SHARED_PREFIX_MAX_BT
+        and 1 <= suffix_blocks <= SHARED_PREFIX_MAX_BT
+    )
+
+
+def shared_prefix_decode_attention(
+    q: torch.Tensor,
+    k_cache: torch.Tensor,
+    v_cache: torch.Tensor,
+    prefix_table: torch.Tensor,
+    prefix_len: torch.Tensor,
+    block_tables: torch.Tensor,
+    context_lens: torch.Tensor,
+    scale: float,
+    softcap: float = 0.0,
+    window: int = 0,
+    out: Optional[torch.Tensor] = None,
+) -> torch.Tensor:
+    """Decode attention for a batch that shares one prefix: sequence b attends
+    to `prefix_len` tokens ([1] int32, on q's device, a multiple of the block
+    size) through `prefix_table` ([Wp] int32) and then to `context_lens[b]`
+    tokens through `block_tables[b]`. On the GPU the prefix is attended once
+    per 128 query rows instead of once per sequence (cascade attention);
+    outside the kernels' envelope the tables are concatenated and the plain
+    decode op runs: same answer, no saving. Rows with context_lens <= 0 are
+    not written (pass `out` to keep their content)."""
+    if not _use_hip(q):
+        res = torch_ref.shared_prefix_decode_attention(
+            q, k_cache, v_cache, prefix_table, prefix_len, block_tables,
+            context_lens, scale, softcap, window)
+        if out is None:
+            return res
+        live = context_lens > 0
+        out[live] = res[live]
+        return out
+    keep_dead_rows = out is not None
+    if out is None:
+        out = torch.empty_like(q)
+    H, D = q.shape[1], q.shape[2]
+    KVH, bs = k_cache.shape[1], k_cache.shape[2]
+    if shared_prefix_kernel_supported(
+            q.dtype, k_cache.dtype, D, H // KVH, bs, prefix_table.shape[0],
+            block_tables.shape[1]):
+        _EXT.shared_prefix_decode_attention(
+            out, q, k_cache, v_cache, prefix_table, prefix_len, block_tables,
+            context_lens, scale, softcap, window)
+        return out
+    tables, lens = torch_ref.concat_prefix_tables(
+        prefix_table, prefix_len, block_tables, context_lens, bs)
+    # the plain op's split-KV merge writes rows of empty sequences too
+    res = torch.empty_like(q) if keep_dead_rows else out
+    _EXT.paged_decode_attention(
+        res, q, k_cache, v_cache, tables, lens, scale, softcap, window)
+    if keep_dead_rows:
+        out.copy_(torch.where((lens > 0)[:, None, None], res, out))
+    return out
+
+
 def varlen_prefill_attention(
     q: torch.Tensor,
     k: torch.Tensor,

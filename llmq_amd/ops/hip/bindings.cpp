@@ -586,7 +586,10 @@ template <typename T>
 void launch_decode(at::Tensor& out, const at::Tensor& q, const at::Tensor& kc,
                    const at::Tensor& vc, const at::Tensor& bt,
                    const at::Tensor& cl, double scale, double softcap,
-                   long window) {
+                   long window, at::Tensor* partials = nullptr) {
+  // partials != nullptr (shared-prefix suffix pass): the MFMA family runs
+  // with at least two z-slices, so pd_store leaves its raw fp32 partials in
+  // scratch; the merge is the caller's and the scratch is handed back.
   const int B = q.size(0), H = q.size(1), D = q.size(2);
   const int KVH = kc.size(1);
   const int bs = kc.size(2);
@@ -606,6 +609,7 @@ void launch_decode(at::Tensor& out, const at::Tensor& q, const at::Tensor& kc,
       // merge fp32 partials. Target ≥512 workgroups (2 resident per CU).
       int nsplit = 1;
       while (B * KVH * nsplit < 512 && nsplit < 16) nsplit *= 2;
+      if (partials && nsplit < 2) nsplit = 2;
       at::Tensor scratch;
       float* scratch_ptr = nullptr;
       if (nsplit > 1) {
@@ -629,7 +633,7 @@ void launch_decode(at::Tensor& out, const at::Tensor& q, const at::Tensor& kc,
                            H, KVH, bs, max_blocks, (float)scale,
                            (float)softcap, (int)window, q.stride(0),
                            out.stride(0));
-        if (nsplit > 1) {
+        if (nsplit > 1 && !partials) {
           hipLaunchKernelGGL((decode_splitkv_merge_kernel<HD>),
                              dim3(B, KVH, G), dim3(64), 0, stream(),
                              reinterpret_cast<BF*>(out.data_ptr()),
@@ -710,9 +714,11 @@ void launch_decode(at::Tensor& out, const at::Tensor& q, const at::Tensor& kc,
           }
         });
       });
+      if (partials) *partials = scratch;
       return;
     }
   }
+  TORCH_CHECK(!partials, "raw partials need the MFMA decode path");
   // The VALU fallback reads the cache as T; an fp8 cache reaching it would
   // be silently reinterpreted as bf16 (garbage, no error).
   TORCH_CHECK(kc.scalar_type() != at::kFloat8_e4m3fn,
@@ -745,6 +751,91 @@ void paged_decode_attention(at::Tensor out, at::Tensor q, at::Tensor k_cache,
   dispatch_dtype(q, "paged_decode_attention", [&]<typename T>() {
     launch_decode<T>(out, q, k_cache, v_cache, block_tables, context_lens,
                      scale, softcap, window);
+  });
+}
+
+// Cascade attention for a batch whose sequences share one prefix: the prefix
+// pass (all B*G query rows of a kv head against the shared blocks, K/V staged
+// once per 128-row tile), the suffix pass (the MFMA decode family, unchanged,
+// leaving raw partials) and the merge of the two by their softmax statistics.
+void shared_prefix_decode_attention(at::Tensor out, at::Tensor q,
+                                    at::Tensor k_cache, at::Tensor v_cache,
+                                    at::Tensor prefix_table,
+                                    at::Tensor prefix_len,
+                                    at::Tensor block_tables,
+                                    at::Tensor context_lens, double scale,
+                                    double softcap, long window) {
+  using BF = __hip_bfloat16;
+  CHECK_GPU(q);
+  CHECK_LASTDIM(q);
+  CHECK_LASTDIM(out);
+  TORCH_CHECK(q.scalar_type() == at::kBFloat16 && out.scalar_type() == at::kBFloat16 &&
+                  k_cache.scalar_type() == at::kBFloat16 &&
+                  v_cache.scalar_type() == at::kBFloat16,
+              "shared_prefix_decode_attention: bf16 q, out and KV cache only");
+  TORCH_CHECK(q.dim() == 3 && out.sizes() == q.sizes() && q.stride(1) == q.size(2) &&
+                  out.stride(1) == out.size(2),
+              "q/out must be [B, H, D] with contiguous heads");
+  TORCH_CHECK(k_cache.is_contiguous() && v_cache.is_contiguous() &&
+                  k_cache.dim() == 4 && v_cache.sizes() == k_cache.sizes(),
+              "k_cache/v_cache must be contiguous [nb, KVH, bs, D]");
+  const int B = q.size(0), H = q.size(1), D = q.size(2);
+  const int KVH = k_cache.size(1), bs = k_cache.size(2);
+  TORCH_CHECK(k_cache.size(3) == D && KVH > 0 && H % KVH == 0, "head layout mismatch");
+  const int G = H / KVH;
+  TORCH_CHECK((D == 128 || D == 256) && G <= 16 && (bs == 16 || bs == 32),
+              "shared_prefix_decode_attention: head_dim 128/256, group <= 16, "
+              "block_size 16/32; got head_dim=", D, " group=", G, " block_size=", bs);
+  TORCH_CHECK(prefix_table.is_cuda() && prefix_table.scalar_type() == at::kInt &&
+                  prefix_table.dim() == 1 && prefix_table.is_contiguous() &&
+                  prefix_table.size(0) >= 1 && prefix_table.size(0) <= SP_MAX_BT,
+              "prefix_table must be a contiguous int32 [Wp] GPU tensor, 1 <= Wp <= ",
+              SP_MAX_BT);
+  TORCH_CHECK(prefix_len.is_cuda() && prefix_len.scalar_type() == at::kInt &&
+                  prefix_len.numel() == 1,
+              "prefix_len must be an int32 [1] GPU tensor");
+  TORCH_CHECK(block_tables.is_cuda() && block_tables.scalar_type() == at::kInt &&
+                  block_tables.dim() == 2 && block_tables.is_contiguous() &&
+                  block_tables.size(0) == B && block_tables.size(1) >= 1 &&
+                  block_tables.size(1) <= PD_MAX_BT,
+              "block_tables must be a contiguous int32 [B, W] GPU tensor, W <= ",
+              PD_MAX_BT);
+  TORCH_CHECK(context_lens.is_cuda() && context_lens.scalar_type() == at::kInt &&
+                  context_lens.dim() == 1 && context_lens.is_contiguous() &&
+                  context_lens.size(0) == B,
+              "context_lens must be a contiguous int32 [B] GPU tensor");
+  if (B == 0) return;
+  const int wp = prefix_table.size(0);
+  // Key split of the prefix pass: enough workgroups to cover the chip, from
+  // the SHAPES only (prefix_len stays on the device), at most one per chunk
+  // of the longest prefix the table can hold.
+  const int tiles = (B * G + SP_ROWS - 1) / SP_ROWS;
+  const int cap_chunks = (wp * bs + SP_KT - 1) / SP_KT;
+  int np = (256 + tiles * KVH - 1) / (tiles * KVH);
+  np = std::max(1, std::min(np, std::min(16, cap_chunks)));
+  at::Tensor prefix_part =
+      at::empty({(long)B, KVH, np, G, D + 2}, q.options().dtype(at::kFloat));
+  dispatch_head_dim<128, 256>(D, [&]<int HD>() {
+    hipLaunchKernelGGL((shared_prefix_attention_kernel<HD>), dim3(tiles, KVH, np),
+                       dim3(SP_NW * 64), 0, stream(),
+                       prefix_part.data_ptr<float>(),
+                       reinterpret_cast<const BF*>(q.data_ptr()),
+                       reinterpret_cast<const BF*>(k_cache.data_ptr()),
+                       reinterpret_cast<const BF*>(v_cache.data_ptr()),
+                       prefix_table.data_ptr<int>(), prefix_len.data_ptr<int>(),
+                       context_lens.data_ptr<int>(), B, H, KVH, bs, wp,
+                       (float)scale, (float)softcap, (int)window, q.stride(0));
+  });
+  at::Tensor suffix_part;
+  launch_decode<BF>(out, q, k_cache, v_cache, block_tables, context_lens, scale,
+                    softcap, window, &suffix_part);
+  const int ns = suffix_part.size(2);
+  dispatch_head_dim<128, 256>(D, [&]<int HD>() {
+    hipLaunchKernelGGL((shared_prefix_merge_kernel<HD>), dim3(B, KVH, G), dim3(64),
+                       0, stream(), reinterpret_cast<BF*>(out.data_ptr()),
+                       suffix_part.data_ptr<float>(), prefix_part.data_ptr<float>(),
+                       prefix_len.data_ptr<int>(), context_lens.data_ptr<int>(),
+                       KVH, G, ns, np, wp, bs, out.stride(0));
   });
 }
 
@@ -1135,6 +1226,7 @@ TORCH_LIBRARY(llmq_amd, m) {
   m.def("gelu_tanh_and_mul(Tensor(a!) out, Tensor input) -> ()");
   m.def("rope_inplace(Tensor(a!) q, Tensor(b!) k, Tensor positions, Tensor cos_sin) -> ()");
   m.def("reshape_and_cache(Tensor key, Tensor value, Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor slot_mapping) -> ()");
+  m.def("shared_prefix_decode_attention(Tensor(a!) out, Tensor q, Tensor k_cache, Tensor v_cache, Tensor prefix_table, Tensor prefix_len, Tensor block_tables, Tensor context_lens, float scale, float softcap, int window) -> ()");
   m.def("paged_decode_attention(Tensor(a!) out, Tensor q, Tensor k_cache, Tensor v_cache, Tensor block_tables, Tensor context_lens, float scale, float softcap, int window) -> ()");
   m.def("varlen_prefill_attention(Tensor(a!) out, Tensor q, Tensor k, Tensor v, Tensor cu_seqlens, Tensor cu_seqlens_k, int max_seqlen, float scale, float softcap, int window) -> ()");
   m.def("sample_gumbel_argmax(Tensor(a!) out, Tensor(b!) keys, Tensor logits, Tensor temps, Tensor req_seeds, Tensor req_pos, int seed, int step, Tensor? bounds=None, float softcap=0.0, Tensor? pen_table=None, Tensor? pen_slots=None, Tensor? pen_params=None) -> ()");
@@ -1161,6 +1253,7 @@ TORCH_LIBRARY_IMPL(llmq_amd, CUDA, m) {
   m.impl("rope_inplace", &rope_inplace);
   m.impl("reshape_and_cache", &reshape_and_cache);
   m.impl("paged_decode_attention", &paged_decode_attention);
+  m.impl("shared_prefix_decode_attention", &shared_prefix_decode_attention);
   m.impl("varlen_prefill_attention", &varlen_prefill_attention);
   m.impl("sample_gumbel_argmax", &sample_gumbel_argmax);
   m.impl("topk_topp_bound", &topk_topp_bound);

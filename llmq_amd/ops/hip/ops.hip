@@ -5,6 +5,7 @@
 #include "kvcache.hip"
 #include "prefill_attention.hip"
 #include "decode_attention.hip"
+#include "shared_prefix_attention.hip"
 #include "skinny_gemm.hip"
 #include "sampling.hip"
 #include "bindings.cpp"

@@ -279,6 +279,48 @@ def paged_decode_attention(
     return out
 
 
+def concat_prefix_tables(
+    prefix_table: torch.Tensor,  # [Wp] int32
+    prefix_len: torch.Tensor,  # [1] int32, a multiple of block_size
+    block_tables: torch.Tensor,  # [B, W] int32
+    context_lens: torch.Tensor,  # [B] int32
+    block_size: int,
+) -> "Tuple[torch.Tensor, torch.Tensor]":
+    """Block tables [B, Wp + W] and lengths of the whole contexts: row b is
+    the prefix blocks followed by block_tables[b]. Tensor ops only (no host
+    read of prefix_len). Rows with context_lens <= 0 keep length 0."""
+    Wp, W = prefix_table.shape[0], block_tables.shape[1]
+    pb = (prefix_len.reshape(1).long() // block_size).clamp(0, Wp)
+    idx = torch.arange(Wp + W, device=block_tables.device)
+    from_prefix = prefix_table.long()[idx.clamp(max=Wp - 1)]
+    from_suffix = block_tables.long()[:, (idx - pb).clamp(0, W - 1)]
+    tables = torch.where(idx < pb, from_prefix, from_suffix).to(torch.int32)
+    lens = torch.where(context_lens > 0, context_lens + pb * block_size,
+                       torch.zeros_like(context_lens)).to(torch.int32)
+    return tables.contiguous(), lens
+
+
+def shared_prefix_decode_attention(
+    q: torch.Tensor,
+    k_cache: torch.Tensor,
+    v_cache: torch.Tensor,
+    prefix_table: torch.Tensor,  # [Wp] int32, blocks every sequence shares
+    prefix_len: torch.Tensor,  # [1] int32 tokens, a multiple of block_size
+    block_tables: torch.Tensor,  # [B, W] int32, each sequence's own blocks
+    context_lens: torch.Tensor,  # [B] int32 tokens behind the prefix
+    scale: float,
+    softcap: float = 0.0,
+    window: int = 0,
+) -> torch.Tensor:
+    """Decode attention of sequences that share one prefix (the definition):
+    sequence b attends to prefix_len tokens through prefix_table, then to
+    context_lens[b] tokens through block_tables[b]."""
+    tables, lens = concat_prefix_tables(
+        prefix_table, prefix_len, block_tables, context_lens, k_cache.shape[2])
+    return paged_decode_attention(q, k_cache, v_cache, tables, lens, scale,
+                                  softcap, window)
+
+
 def varlen_prefill_attention(
     q: torch.Tensor,  # [Tq, num_heads, head_dim]
     k: torch.Tensor,  # [Tk, kv_heads, head_dim]

@@ -386,6 +386,10 @@ class EngineWorker(BaseWorker):
             kwargs["max_model_len"] = max_len
         if self.config.enable_prefix_caching:
             kwargs["enable_prefix_caching"] = True
+        if self.config.shared_prefix_decode:
+            # needs the shared blocks that prefix caching creates
+            kwargs["enable_prefix_caching"] = True
+            kwargs["shared_prefix_decode"] = True
         # a pipeline stage's own setting wins over the environment's
         quantization = self.stage_config.get("quantization", self.config.quantization)
         if quantization != "none":
