@@ -243,9 +243,10 @@ def worker() -> None:
 @click.option("--shared-prefix-decode", is_flag=True, default=False,
               help="Decode attention reads the prompt head shared by the whole "
                    "batch once (cascade); turns prefix caching on")
-@click.option("--quantization", type=click.Choice(["none", "fp8"]), default=None,
+@click.option("--quantization", type=click.Choice(["none", "fp8", "mxfp4"]), default=None,
               help="fp8: W8A8 layer projections, quantised at load "
-                   "(halves weight memory); default none or LLMQ_QUANTIZATION")
+                   "(halves weight memory); mxfp4: W4A8, MXFP4 weights "
+                   "(4.25 bits each); default none or LLMQ_QUANTIZATION")
 @click.option("--engine-overrides", default=None,
               help='JSON dict of EngineConfig overrides, e.g. \'{"enforce_eager": true}\'')
 @click.option("--data-parallel-size", "-dp", type=int, default=None,

@@ -151,7 +151,7 @@ class Config(BaseModel):
     )
     quantization: str = Field(
         default_factory=lambda: _env("LLMQ_QUANTIZATION", "none"),
-        description="Weight/activation quantisation of the engine: none | fp8",
+        description="Weight/activation quantisation of the engine: none | fp8 | mxfp4",
     )
     temperature: float = Field(
         default_factory=lambda: _env_float("LLMQ_TEMPERATURE", 0.7),

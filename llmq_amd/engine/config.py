@@ -40,7 +40,10 @@ class EngineConfig:
     shared_prefix_decode: bool = False
     # "none" = weights in the compute dtype; "fp8" = W8A8: the layer
     # projection weights stored as OCP e4m3 with a per-output-channel scale,
-    # activations quantised per row on the fly, fp8 GEMMs. Opt-in.
+    # activations quantised per row on the fly, fp8 GEMMs. "mxfp4" = W4A8:
+    # the same fp8 activations against OCP MXFP4 weights (4.25 bits each)
+    # through the scaled-MFMA GEMM; projections outside that kernel's
+    # envelope stay fp8. Opt-in.
     quantization: str = "none"
 
     def __post_init__(self) -> None:
@@ -49,21 +52,23 @@ class EngineConfig:
             raise ValueError("shared_prefix_decode requires enable_prefix_caching")
 
     def _check_quantization(self) -> None:
-        if self.quantization not in ("none", "fp8"):
+        if self.quantization not in ("none", "fp8", "mxfp4"):
             raise ValueError(
-                f"unknown quantization {self.quantization!r} (expected 'none' or 'fp8')"
+                f"unknown quantization {self.quantization!r} "
+                "(expected 'none', 'fp8' or 'mxfp4')"
             )
 
     def resolve_quantization(self, device: torch.device) -> Optional[str]:
-        """None, or "fp8" after checking that the device can run it: the fp8
-        GEMMs need bf16 compute on the GPU; on CPU the fp32 fake-quant
-        reference path runs."""
+        """None, or "fp8" / "mxfp4" after checking that the device can run
+        it: the quantised GEMMs need bf16 compute on the GPU; on CPU the fp32
+        fake-quant reference path runs."""
         self._check_quantization()
         if self.quantization == "none":
             return None
         if device.type == "cuda" and self.resolve_dtype(device) != torch.bfloat16:
-            raise ValueError("quantization=fp8 requires bf16 execution on GPU")
-        return "fp8"
+            raise ValueError(
+                f"quantization={self.quantization} requires bf16 execution on GPU")
+        return self.quantization
 
     def resolve_device(self) -> torch.device:
         if self.device == "auto":

@@ -20,6 +20,7 @@ the model set the reference serves through vLLM). Design notes, MI355X-first:
 
 from __future__ import annotations
 
+import logging
 import math
 import os
 from typing import Dict, List, Optional, Union
@@ -34,6 +35,7 @@ from llmq_amd.engine.kv_cache import KVCache
 from llmq_amd.engine.model_specs import ModelSpec
 from llmq_amd.parallel import get_tp_group
 
+logger = logging.getLogger(__name__)
 
 # Decode projection GEMMs through the hand-written skinny-M kernel
 # (ops.skinny_gemm) instead of hipBLASLt. Opt-in while A/B-ing
@@ -51,7 +53,10 @@ def _proj(x: torch.Tensor, w: torch.Tensor, bias=None) -> torch.Tensor:
 
 # The four projection weights of a layer: the tensors quantization="fp8"
 # stores as float8_e4m3fn [N, K] with an fp32 per-output-channel scale [N]
-# in LayerWeights.<name>_scale.
+# in LayerWeights.<name>_scale. quantization="mxfp4" stores the packed e2m1
+# codes (uint8) there and the packed e8m0 block scales (uint8) in
+# <name>_scale; a projection outside the MXFP4 kernel's envelope keeps the
+# fp8 form, so the dtype of the stored weight says which GEMM runs.
 LINEARS = ("qkv", "o", "gate_up", "down")
 
 
@@ -90,9 +95,12 @@ class CausalLM:
         tp_size: int = 1,
         quantization: Optional[str] = None,
     ):
-        if quantization not in (None, "fp8"):
+        if quantization not in (None, "fp8", "mxfp4"):
             raise ValueError(f"unknown quantization {quantization!r}")
-        self.fp8 = quantization == "fp8"
+        self.quantization = quantization
+        # activations travel quantised (fp8 rows + scale) between the kernels
+        self.act_quant = quantization is not None
+        self._fp8_fallbacks: set = set()  # mxfp4: projections logged as fp8
         self.spec = spec
         self.device = device
         self.dtype = dtype
@@ -145,25 +153,35 @@ class CausalLM:
         }[name]
 
     def _empty_linear(self, name: str) -> Optional[torch.Tensor]:
-        # fp8: no storage in the compute dtype; set_linear installs the
+        # quantised: no storage in the compute dtype; set_linear installs the
         # quantised tensor, one projection at a time
-        return None if self.fp8 else self._empty(*self.linear_shape(name))
+        return None if self.act_quant else self._empty(*self.linear_shape(name))
 
     @torch.no_grad()
     def set_linear(self, lw: LayerWeights, name: str, src: torch.Tensor) -> None:
         """Install this rank's shard `src` [N, K] (any dtype or device) as
-        projection `name` of `lw`. Under fp8 it is quantised here, after
+        projection `name` of `lw`. A quantised model quantises it here, after
         sharding, so a row-sharded projection gets scales over its local K;
         the copy in the compute dtype lives only inside this call, and the
-        model never holds two full sets of weights."""
+        model never holds two full sets of weights. Under mxfp4 a projection
+        whose local [N, K] the MXFP4 kernel cannot take is stored as fp8."""
         if tuple(src.shape) != self.linear_shape(name):
             raise ValueError(
                 f"shape mismatch: {self.linear_shape(name)} vs {tuple(src.shape)}")
-        if not self.fp8:
+        if not self.act_quant:
             getattr(lw, name).copy_(src.to(self.dtype))
             return
         w = src.to(device=self.device, dtype=torch.bfloat16)
-        w_q, w_scale = torch_ref.quant_fp8_weight(w)
+        N, K = w.shape
+        if self.quantization == "mxfp4" and ops.mxfp4_supported(K, N):
+            w_q, w_scale = ops.mxfp4_pack_weight(*torch_ref.quant_mxfp4_weight(w))
+        else:
+            if self.quantization == "mxfp4" and name not in self._fp8_fallbacks:
+                self._fp8_fallbacks.add(name)
+                logger.info(
+                    "mxfp4: projection %s [N=%d, K=%d] is outside the MXFP4 "
+                    "kernel's envelope (K %% 128, N %% 16); stored as fp8", name, N, K)
+            w_q, w_scale = torch_ref.quant_fp8_weight(w)
         setattr(lw, name, w_q)
         setattr(lw, name + "_scale", w_scale)
 
@@ -214,10 +232,10 @@ class CausalLM:
                 t.copy_(cpu.to(t.dtype))
 
         def fill_linear(lw: LayerWeights, name: str, std: float) -> None:
-            if not self.fp8:
+            if not self.act_quant:
                 fill(getattr(lw, name), std)
                 return
-            # the tensor the unquantised model would hold, then its fp8 form
+            # the tensor the unquantised model would hold, then its quantised form
             w = self._empty(*self.linear_shape(name))
             fill(w, std)
             self.set_linear(lw, name, w)
@@ -245,6 +263,10 @@ class CausalLM:
         if not self.spec.tied_embeddings:
             fill(self.lm_head, std)
 
+    @property
+    def fp8(self) -> bool:
+        return self.quantization == "fp8"
+
     def named_tensors(self) -> Dict[str, torch.Tensor]:
         out = {"embedding": self.embedding, "final_norm": self.final_norm}
         if not self.spec.tied_embeddings:
@@ -265,7 +287,7 @@ class CausalLM:
             if lw.post_attn_norm is not None:
                 out[p + "post_attn_norm"] = lw.post_attn_norm
                 out[p + "post_mlp_norm"] = lw.post_mlp_norm
-            if self.fp8:
+            if self.act_quant:
                 for name in LINEARS:
                     out[p + name + "_scale"] = getattr(lw, name + "_scale")
         return out
@@ -278,15 +300,19 @@ class CausalLM:
     def _norm(self, x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
         return ops.rmsnorm(x, w, self.spec.rms_eps, self.norm_offset)
 
-    # Under fp8 the input of every layer projection travels as a pair
+    # In a quantised model the input of every layer projection travels as a pair
     # (q [T, K] float8_e4m3fn, scale [T] fp32) from the kernel that produced
     # it (a fused norm, the gated activation, or quant_fp8_rows after
-    # attention) to the fp8 GEMM; otherwise it is the plain tensor.
+    # attention) to the fp8 or MXFP4 GEMM, which take the same pair;
+    # otherwise it is the plain tensor.
 
     def _linear(self, h, lw: LayerWeights, name: str, bias=None) -> torch.Tensor:
         w = getattr(lw, name)
-        if self.fp8:
-            return ops.fp8_linear(h[0], h[1], w, getattr(lw, name + "_scale"), bias)
+        if self.act_quant:
+            scale = getattr(lw, name + "_scale")
+            if w.dtype == torch.uint8:
+                return ops.mxfp4_linear(h[0], h[1], (w, scale), bias)
+            return ops.fp8_linear(h[0], h[1], w, scale, bias)
         return _proj(h, w, bias)
 
     def _add_norm(self, x, residual, w_post, w, quant: bool):
@@ -354,7 +380,7 @@ class CausalLM:
             x = x * math.sqrt(s.hidden_size)
             x = x.to(self.dtype)
         residual = x
-        fp8 = self.fp8
+        fp8 = self.act_quant
         if fp8:
             h = ops.rmsnorm_quant_fp8(
                 x, self.layers[0].input_norm, s.rms_eps, self.norm_offset)

@@ -208,6 +208,63 @@ def fp8_linear(
         bias=bias, out_dtype=torch.bfloat16)
 
 
+# ------------------------------------------------ MXFP4 weights (W4A8) --
+# Weights in OCP MXFP4 (torch_ref.quant_mxfp4_weight), activations as the
+# fp8 mode carries them. On the GPU the GEMM is the hand-written scaled-MFMA
+# kernel of hip/mxfp4_gemm.hip, which reads the weight in fragment order.
+
+quant_mxfp4_weight = torch_ref.quant_mxfp4_weight
+dequant_mxfp4_weight = torch_ref.dequant_mxfp4_weight
+
+
+def mxfp4_supported(K: int, N: int) -> bool:
+    """The envelope of the MXFP4 GEMM kernel for a weight [N, K]."""
+    return K > 0 and N > 0 and K % 128 == 0 and N % 16 == 0
+
+
+def mxfp4_pack_weight(
+    codes: torch.Tensor,   # [N, K/2] uint8
+    scales: torch.Tensor,  # [N, K/32] uint8
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The weight as mxfp4_linear takes it on the tensors' device. On CPU the
+    pair itself. On the GPU the kernel's fragment order, done once at load:
+    codes [N/16, K/128, 64 lanes, 16 B] with lane 16 * kgrp + r holding
+    elements 32 * kgrp .. + 31 of K step s of row 16 * g + r, and scales
+    [N/16, ceil(K/512), 64 lanes, 4 B] with byte j the lane's block scale at
+    K step 4 * q + j (steps past K padded with 127)."""
+    if not codes.is_cuda:
+        return codes, scales
+    N, K = codes.shape[0], codes.shape[1] * 2
+    assert mxfp4_supported(K, N), f"[N={N}, K={K}] outside the MXFP4 kernel's envelope"
+    steps = K // 128
+    pc = codes.view(N // 16, 16, steps, 4, 16).permute(0, 2, 3, 1, 4).contiguous()
+    qsteps = (steps + 3) // 4
+    ps = torch.full((N, qsteps * 4, 4), 127, dtype=torch.uint8, device=codes.device)
+    ps[:, :steps] = scales.view(N, steps, 4)
+    ps = ps.view(N // 16, 16, qsteps, 4, 4).permute(0, 2, 4, 1, 3).contiguous()
+    return pc.view(N // 16, steps, 64, 16), ps.view(N // 16, qsteps, 64, 4)
+
+
+def mxfp4_linear(
+    a_q: torch.Tensor,      # [T, K] float8_e4m3fn
+    a_scale: torch.Tensor,  # [T] fp32 per-row scale
+    w_packed: Tuple[torch.Tensor, torch.Tensor],  # mxfp4_pack_weight's result
+    bias: Optional[torch.Tensor] = None,
+    splitk: int = 0,        # 0 = auto
+) -> torch.Tensor:
+    """(a_q * a_scale[:, None]) @ dequant_mxfp4_weight(w).T + bias. On the GPU
+    the scaled-MFMA kernel, bf16 [T, N] out; on CPU the fp32 fake-quant
+    reference."""
+    codes, scales = w_packed
+    if not _use_hip(a_q):
+        return torch_ref.mxfp4_linear(a_q, a_scale, codes, scales, bias)
+    out = torch.empty(a_q.shape[0], codes.shape[0] * 16, dtype=torch.bfloat16,
+                      device=a_q.device)
+    if a_q.shape[0]:
+        _EXT.mxfp4_gemm(out, a_q, a_scale, codes, scales, bias, splitk)
+    return out
+
+
 # ----------------------------------------------------------------- rope --
 
 

@@ -1004,6 +1004,95 @@ void skinny_gemm(at::Tensor out, at::Tensor x, at::Tensor w,
                      slabs.data_ptr<float>(), bias_ptr, z, MN, N);
 }
 
+// ------------------------------------------------- MXFP4 (W4A8) GEMM --
+
+// out[M,N] bf16 = (a_q . dequant(w)^T) * a_scale[:,None] + bias with w as
+// mxfp4_pack_weight laid it out (see mxfp4_gemm.hip). splitk: 0 = auto.
+void mxfp4_gemm(at::Tensor out, at::Tensor a_q, at::Tensor a_scale,
+                at::Tensor w_codes, at::Tensor w_scales,
+                c10::optional<at::Tensor> bias, long splitk) {
+  CHECK_GPU(out);
+  CHECK_GPU(a_q);
+  CHECK_GPU(a_scale);
+  CHECK_GPU(w_codes);
+  CHECK_GPU(w_scales);
+  TORCH_CHECK(a_q.dim() == 2 && out.dim() == 2);
+  CHECK_LASTDIM(a_q);
+  TORCH_CHECK(a_q.scalar_type() == at::kFloat8_e4m3fn, "a_q must be float8_e4m3fn");
+  TORCH_CHECK(out.scalar_type() == at::kBFloat16 && out.is_contiguous());
+  const int M = a_q.size(0), K = a_q.size(1), N = out.size(1);
+  TORCH_CHECK(out.size(0) == M && M > 0 && N > 0 && K > 0);
+  TORCH_CHECK(K % MX4_BK == 0, "K must be a multiple of 128");
+  TORCH_CHECK(N % 16 == 0, "N must be a multiple of 16");
+  TORCH_CHECK(a_scale.scalar_type() == at::kFloat && a_scale.numel() == M &&
+              a_scale.is_contiguous(), "a_scale must be contiguous fp32 [M]");
+  const int ksteps = K / MX4_BK;
+  const int qsteps = (ksteps + 3) / 4;
+  TORCH_CHECK(w_codes.scalar_type() == at::kByte && w_codes.is_contiguous() &&
+              w_codes.numel() == (long)N * K / 2,
+              "w_codes must be the packed uint8 codes of an [N, K] weight");
+  TORCH_CHECK(w_scales.scalar_type() == at::kByte && w_scales.is_contiguous() &&
+              w_scales.numel() == (long)(N / 16) * qsteps * 256,
+              "w_scales must be the packed uint8 scales of an [N, K] weight");
+  // A staging and the B loads move aligned 16-byte granules
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(a_q.data_ptr()) % 16 == 0 &&
+              a_q.stride(0) % 16 == 0, "a_q rows must be 16-byte aligned");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(w_codes.data_ptr()) % 16 == 0 &&
+              reinterpret_cast<uintptr_t>(w_scales.data_ptr()) % 4 == 0);
+  TORCH_CHECK(splitk >= 0, "splitk must be >= 0 (0 = auto)");
+  const __hip_bfloat16* bias_ptr = nullptr;
+  if (bias.has_value() && bias->defined()) {
+    CHECK_GPU((*bias));
+    TORCH_CHECK(bias->scalar_type() == at::kBFloat16 && bias->numel() == N &&
+                bias->is_contiguous(), "bias must be contiguous bf16 [N]");
+    bias_ptr = reinterpret_cast<const __hip_bfloat16*>(bias->data_ptr());
+  }
+  const bool tall = M > 64;  // 256x128 tile; else the 32x64 weight-stream tile
+  const int BM = tall ? 256 : 32, BN = tall ? 128 : 64;
+  const int mt = (M + BM - 1) / BM;
+  const int nt = (N + BN - 1) / BN;
+  int z = (int)splitk;
+  if (z <= 0) {  // auto: fill the chip (>= 256 blocks), keep >= 4 K steps/slice
+    z = 1;
+    while (mt * nt * z < 256 && ksteps / (z * 2) >= 4 && z < 16) z *= 2;
+  }
+  z = std::min(z, ksteps);
+  // the kernel gives a slice ceil(ksteps / z) steps: drop the slices that
+  // leaves empty, so the reduce reads written slabs only
+  const int per = (ksteps + z - 1) / z;
+  z = (ksteps + per - 1) / per;
+  const dim3 grid(mt, nt, z);
+  at::Tensor slabs;
+  void* dst = out.data_ptr();
+  if (z > 1) {
+    slabs = at::empty({z, (long)M * N}, out.options().dtype(at::kFloat));
+    dst = slabs.data_ptr();
+  }
+  auto launch = [&]<int TBM, int TBN, int WM, int WN, bool SPLIT, bool NT_B>() {
+    hipLaunchKernelGGL((mxfp4_gemm_kernel<TBM, TBN, WM, WN, SPLIT, NT_B>), grid,
+                       dim3(WM * WN * WAVE), 0, stream(), dst,
+                       reinterpret_cast<const unsigned char*>(a_q.data_ptr()),
+                       a_scale.data_ptr<float>(), w_codes.data_ptr<uint8_t>(),
+                       w_scales.data_ptr<uint8_t>(), SPLIT ? nullptr : bias_ptr,
+                       M, N, K, (long)a_q.stride(0));
+  };
+  if (tall) {
+    if (z > 1) launch.template operator()<256, 128, 4, 2, true, false>();
+    else launch.template operator()<256, 128, 4, 2, false, false>();
+  } else {
+    if (z > 1) launch.template operator()<32, 64, 1, 4, true, true>();
+    else launch.template operator()<32, 64, 1, 4, false, true>();
+  }
+  if (z == 1) return;
+  const long MN = (long)M * N;
+  const long blocks = (MN / 4 + 255) / 256;
+  hipLaunchKernelGGL(mxfp4_gemm_reduce_kernel, dim3(blocks), dim3(256), 0,
+                     stream(),
+                     reinterpret_cast<__hip_bfloat16*>(out.data_ptr()),
+                     slabs.data_ptr<float>(), a_scale.data_ptr<float>(),
+                     bias_ptr, z, MN, N);
+}
+
 // ------------------------------------------------------------- sampling --
 
 // Logits arrive as the lm_head GEMM stored them (bf16/half) or as fp32;
@@ -1233,6 +1322,7 @@ TORCH_LIBRARY(llmq_amd, m) {
   m.def("topk_topp_bound(Tensor(a!) out_bound, Tensor logits, Tensor temps, Tensor top_ps, Tensor top_ks, float softcap=0.0, Tensor? min_ps=None, Tensor? pen_table=None, Tensor? pen_slots=None, Tensor? pen_params=None) -> ()");
   m.def("penalty_count_tokens(Tensor(a!) table, Tensor slots, Tensor tokens) -> ()");
   m.def("skinny_gemm(Tensor(a!) out, Tensor x, Tensor w, Tensor? bias, int splitk) -> ()");
+  m.def("mxfp4_gemm(Tensor(a!) out, Tensor a_q, Tensor a_scale, Tensor w_codes, Tensor w_scales, Tensor? bias, int splitk) -> ()");
   m.def("quant_fp8_rows(Tensor(a!) q, Tensor(b!) scale, Tensor x) -> ()");
   m.def("silu_and_mul_quant_fp8(Tensor(a!) q, Tensor(b!) scale, Tensor gate_up) -> ()");
   m.def("gelu_tanh_and_mul_quant_fp8(Tensor(a!) q, Tensor(b!) scale, Tensor gate_up) -> ()");
@@ -1260,6 +1350,7 @@ TORCH_LIBRARY_IMPL(llmq_amd, CUDA, m) {
   m.impl("penalty_count_tokens", &penalty_count_tokens);
   m.impl("token_logprobs", &token_logprobs);
   m.impl("skinny_gemm", &skinny_gemm);
+  m.impl("mxfp4_gemm", &mxfp4_gemm);
   m.impl("norm_add_norm", &norm_add_norm);
   m.impl("quant_fp8_rows", &quant_fp8_rows);
   m.impl("silu_and_mul_quant_fp8", &silu_and_mul_quant_fp8);

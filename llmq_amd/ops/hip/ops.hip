@@ -7,5 +7,6 @@
 #include "decode_attention.hip"
 #include "shared_prefix_attention.hip"
 #include "skinny_gemm.hip"
+#include "mxfp4_gemm.hip"
 #include "sampling.hip"
 #include "bindings.cpp"

@@ -147,6 +147,73 @@ def fp8_linear(
     return out if bias is None else out + bias.float()
 
 
+# ---- MXFP4 weights (OCP Microscaling v1.0): blocks of 32 consecutive
+# K-elements share an e8m0 exponent, elements are e2m1.
+
+MXFP4_BLOCK = 32
+# value of code 0..7 (exponent * 2 + mantissa); codes 8..15 are the negatives
+_E2M1_VALUES = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
+
+
+def _scale_pow2(x: torch.Tensor, n: torch.Tensor) -> torch.Tensor:
+    """x * 2^n, exact, for integer n in [-252, 254]: two multiplications by
+    powers of two built from their bits (a device's pow may be inexact, and
+    2^-127 is subnormal)."""
+    half = n // 2
+    for e in (half, n - half):
+        x = x * ((e.to(torch.int32) + 127) << 23).view(torch.float32)
+    return x
+
+
+def quant_mxfp4_weight(w: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """MXFP4 form of the bf16 rounding of w [N, K], K % 32 == 0: (codes uint8
+    [N, K/2], scales uint8 [N, K/32]). Per block the shared exponent is X =
+    floor(log2(amax)) - 2 clamped to [-127, 127] (-127 for an all-zero
+    block), stored as X + 127; elements are w / 2^X rounded to the e2m1 grid
+    {0, .5, 1, 1.5, 2, 3, 4, 6}, to nearest with ties to the even mantissa,
+    saturating at 6. Element 2j of a row is the low nibble of byte j; a code
+    is sign * 8 + exponent * 2 + mantissa. Every step is exact in fp32, so
+    any device gives the same bytes."""
+    N, K = w.shape
+    assert K % MXFP4_BLOCK == 0, f"K={K} is not a multiple of {MXFP4_BLOCK}"
+    wb = w.to(torch.bfloat16).float().view(N, K // MXFP4_BLOCK, MXFP4_BLOCK)
+    amax = wb.abs().amax(dim=-1)
+    _, e = torch.frexp(amax)              # amax = m * 2^e, m in [0.5, 1)
+    X = (e - 3).clamp(-127, 127)          # floor(log2(amax)) = e - 1
+    X = torch.where(amax == 0, torch.full_like(X, -127), X)
+    x = _scale_pow2(wb, -X.unsqueeze(-1))
+    a = x.abs().clamp(max=6.0)
+    # grid steps: 0.5 below 2, 1 below 4, 2 above; torch.round is half-to-even,
+    # which on each segment is ties-to-even-mantissa
+    q = torch.where(a < 2, torch.round(a * 2) / 2,
+                    torch.where(a < 4, torch.round(a), torch.round(a / 2) * 2))
+    code = torch.where(q < 2, q * 2, torch.where(q < 4, q + 2, q / 2 + 4))
+    code = (code.to(torch.uint8) | ((x < 0).to(torch.uint8) << 3)).view(N, K)
+    codes = code[:, 0::2] | (code[:, 1::2] << 4)
+    return codes.contiguous(), (X + 127).to(torch.uint8)
+
+
+def dequant_mxfp4_weight(codes: torch.Tensor, scales: torch.Tensor) -> torch.Tensor:
+    """fp32 [N, K] weight that (codes [N, K/2], scales [N, K/32]) stand for."""
+    N = codes.shape[0]
+    lut = torch.tensor(_E2M1_VALUES + tuple(-v for v in _E2M1_VALUES),
+                       dtype=torch.float32, device=codes.device)
+    nib = torch.stack((codes & 0xF, codes >> 4), dim=-1).view(N, -1)
+    w = lut[nib.long()].view(N, -1, MXFP4_BLOCK)
+    return _scale_pow2(w, (scales.to(torch.int32) - 127).unsqueeze(-1)).view(N, -1)
+
+
+def mxfp4_linear(
+    a_q: torch.Tensor, a_scale: torch.Tensor, codes: torch.Tensor,
+    scales: torch.Tensor, bias: Optional[torch.Tensor] = None,
+) -> torch.Tensor:
+    """Fake-quant reference of the W4A8 GEMM: dequantise both operands to
+    fp32, fp32 matmul, add the bias. Returns fp32 [T, N]."""
+    a = a_q.float() * a_scale.unsqueeze(-1)
+    out = a @ dequant_mxfp4_weight(codes, scales).t()
+    return out if bias is None else out + bias.float()
+
+
 def reshape_and_cache(
     key: torch.Tensor,  # [T, kv_heads, head_dim]
     value: torch.Tensor,

@@ -390,7 +390,8 @@ class EngineWorker(BaseWorker):
             # needs the shared blocks that prefix caching creates
             kwargs["enable_prefix_caching"] = True
             kwargs["shared_prefix_decode"] = True
-        # a pipeline stage's own setting wins over the environment's
+        # none | fp8 | mxfp4; a pipeline stage's own setting wins over the
+        # environment's
         quantization = self.stage_config.get("quantization", self.config.quantization)
         if quantization != "none":
             kwargs["quantization"] = str(quantization)
