@@ -30,6 +30,7 @@ _CONTROL_FIELDS = (
     "frequency_penalty",
     "min_p",
     "logprobs",
+    "prompt_logprobs",
 )
 
 
@@ -59,6 +60,8 @@ class Job(BaseModel):
     min_p: Optional[float] = Field(None)
     logprobs: Optional[int] = Field(
         None, description="Return token logprobs with this many alternatives (0-20)")
+    prompt_logprobs: Optional[bool] = Field(
+        None, description="Return the log-probability of every prompt token")
 
     @model_validator(mode="after")
     def _exactly_one_input(self) -> "Job":
@@ -111,6 +114,11 @@ class Result(BaseModel):
     # and the sum of the tokens' logprobs.
     logprobs: Optional[List[Dict[str, Any]]] = Field(None)
     cumulative_logprob: Optional[float] = Field(None)
+    # Jobs that asked for prompt_logprobs: one {"token_id", "token", "logprob"}
+    # per prompt token (the first logprob is null: nothing precedes it), and
+    # the sum of the others.
+    prompt_logprobs: Optional[List[Dict[str, Any]]] = Field(None)
+    prompt_cumulative_logprob: Optional[float] = Field(None)
 
 
 class QueueStats(BaseModel):

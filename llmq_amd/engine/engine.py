@@ -95,6 +95,9 @@ class RequestOutput:
     new_logprobs: Optional[tuple] = None
     logprobs: Optional[List[tuple]] = None
     cumulative_logprob: Optional[float] = None
+    # SamplingParams.prompt_logprobs set, on the finishing output: one
+    # (token_id, logprob) per prompt token, the first logprob None
+    prompt_logprobs: Optional[List[tuple]] = None
 
 
 class LLMEngine:
@@ -386,6 +389,7 @@ class LLMEngine:
         else:
             tokens = self.runner.execute_decode(batch.seqs)
         token_list = tokens.tolist()
+        self.runner.collect_prompt_logprobs()
         if lp_parts is None:
             row_lps = take_lp("main")
         elif lp_parts[0] is None and lp_parts[1] is None:
@@ -454,6 +458,9 @@ class LLMEngine:
                 if seq.logprobs is not None:
                     out.logprobs = seq.logprobs
                     out.cumulative_logprob = float(sum(e[1] for e in seq.logprobs))
+                if seq.prompt_logprobs is not None:
+                    out.prompt_logprobs = list(zip(
+                        seq.token_ids[:seq.prompt_len], seq.prompt_logprobs))
                 prefill_at = self._prefill_done_at.pop(seq.request_id, now)
                 started = seq.prefill_start_time or prefill_at
                 out.queue_wait_ms = (started - seq.arrival_time) * 1000.0

@@ -91,6 +91,10 @@ class ModelRunner:
         # take_logprobs collects them: (asking rows, their k, batch size,
         # then either the entries (CPU) or the pinned record + copy event).
         self._logprobs: Dict[str, tuple] = {}
+        # Prompt logprobs of the latest prefill segment per buffer name, until
+        # collect_prompt_logprobs files them: ([(seq, first, last position)],
+        # host values, copy event or None).
+        self._prompt_lp: Dict[str, tuple] = {}
         # Count table of the repetition/presence/frequency penalties; holds no
         # memory until the first penalised request (PenaltyTable docstring).
         self.penalty_table = PenaltyTable(
@@ -322,12 +326,63 @@ class ModelRunner:
         input_ids = torch.tensor(ids, dtype=torch.long, device=dev)
         positions = torch.tensor(pos, dtype=torch.long, device=dev)
         hidden = self.model.forward(input_ids, positions, self.kv_cache, meta)
+        self._score_prompts(hidden, 0, seqs, chunks, buf_name)
         if not rel_last:
             return torch.empty(0, dtype=torch.long, device=dev)
         last_hidden = hidden[torch.tensor(rel_last, dtype=torch.long, device=dev)]
         logits, cap = self._logits_for_sampling(last_hidden)
         sample_seqs = [s for s, (st, e) in zip(seqs, chunks) if e == s.num_tokens]
         return self._sample(logits, sample_seqs, buf_name, softcap=cap)
+
+    # -- prompt logprobs --------------------------------------------------
+
+    def _score_prompts(self, hidden: torch.Tensor, row0: int, pseqs, chunks,
+                       buf_name: str) -> None:
+        """Prompt logprobs of this step's prefill segment (rows row0.. of
+        `hidden`, the final-norm states): for every sequence that asked, the
+        rows at positions p with p + 1 < prompt_len score token_ids[p + 1].
+        One ops.lm_head_logprobs call, no logits stored, and one copy to the
+        host that collect_prompt_logprobs waits for."""
+        rows: List[int] = []
+        targets: List[int] = []
+        dest: List[tuple] = []
+        base = row0
+        for seq, (start, end) in zip(pseqs, chunks):
+            last = min(end, seq.prompt_len - 1)
+            if seq.prompt_logprobs is not None and last > start:
+                rows.extend(range(base, base + last - start))
+                targets.extend(seq.token_ids[start + 1:last + 1])
+                dest.append((seq, start, last))
+            base += end - start
+        if not rows:
+            return
+        dev = hidden.device
+        idx = torch.tensor([rows, targets], dtype=torch.int32, device=dev)
+        cap = self.model.spec.final_softcap
+        lp = ops.lm_head_logprobs(
+            hidden, self.model.lm_head, idx[0], idx[1],
+            softcap=float(cap) if cap and cap > 0 else 0.0)
+        if dev.type != "cuda":
+            self._prompt_lp[buf_name] = (dest, lp, None)
+            return
+        host = torch.empty(len(rows), dtype=torch.float32, pin_memory=True)
+        host.copy_(lp, non_blocking=True)
+        done = torch.cuda.Event()
+        done.record()
+        self._prompt_lp[buf_name] = (dest, host, done)
+
+    def collect_prompt_logprobs(self) -> None:
+        """File the values _score_prompts left, by prompt position: entry
+        p + 1 of a sequence's list is the score of the row at position p."""
+        for dest, host, done in self._prompt_lp.values():
+            if done is not None:
+                done.synchronize()
+            vals = host.tolist()
+            i = 0
+            for seq, start, last in dest:
+                seq.prompt_logprobs[start + 1:last + 1] = vals[i:i + last - start]
+                i += last - start
+        self._prompt_lp.clear()
 
     # -- mixed (decode rows + ride-along prefill rows, eager) ------------
 
@@ -376,6 +431,7 @@ class ModelRunner:
         input_ids = torch.tensor(ids, dtype=torch.long, device=dev)
         positions = torch.tensor(pos, dtype=torch.long, device=dev)
         hidden = self.model.forward(input_ids, positions, self.kv_cache, meta)
+        self._score_prompts(hidden, nd, pseqs, chunks, "main")
         last_idx = list(range(nd)) + [nd + r for r in rel_last]
         last_hidden = hidden[torch.tensor(last_idx, dtype=torch.long, device=dev)]
         logits, cap = self._logits_for_sampling(last_hidden)

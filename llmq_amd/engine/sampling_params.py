@@ -36,6 +36,11 @@ class SamplingParams:
     # under log_softmax of the model's (soft-capped) logits: before penalties,
     # temperature and top-k/top-p/min_p.
     logprobs: Optional[int] = None
+    # Score the prompt: the log-probability of every prompt token given the
+    # tokens before it (the first has none), under the same distribution.
+    # Such a request reads nothing from the prefix cache: every position needs
+    # its hidden state.
+    prompt_logprobs: bool = False
 
     def __post_init__(self) -> None:
         if self.temperature < 0:

@@ -47,7 +47,7 @@ class Sequence:
         "request_id", "token_ids", "prompt_len", "params", "status",
         "block_table", "arrival_time", "first_token_time", "finish_reason",
         "output_text", "num_preemptions", "prefilled", "prefill_start_time",
-        "uid", "cached_tokens", "logprobs",
+        "uid", "cached_tokens", "logprobs", "prompt_logprobs",
     )
 
     def __init__(self, request_id: str, prompt_token_ids: List[int], params: SamplingParams,
@@ -75,6 +75,11 @@ class Sequence:
         # per generated token; like token_ids it survives preemption
         self.logprobs: Optional[List[tuple]] = (
             [] if params.logprobs is not None else None)
+        # params.prompt_logprobs: log p(token_ids[p] | token_ids[:p]) by
+        # prompt position, filled chunk by chunk as the prompt prefills (a
+        # recompute after preemption writes equal values); entry 0 stays None
+        self.prompt_logprobs: Optional[List[Optional[float]]] = (
+            [None] * self.prompt_len if params.prompt_logprobs else None)
 
     @property
     def num_tokens(self) -> int:
@@ -145,6 +150,8 @@ class Scheduler:
             # Trim oversized prompts from the left (keep the recent window).
             seq.token_ids = seq.token_ids[-self.max_model_len + 1 :]
             seq.prompt_len = len(seq.token_ids)
+            if seq.prompt_logprobs is not None:
+                seq.prompt_logprobs = [None] * seq.prompt_len
         # Reject a prompt the pool could NEVER seat even when empty —
         # otherwise it blocks the head of the waiting queue forever and the
         # engine livelocks on empty steps (has_work() stays true while no
@@ -233,8 +240,12 @@ class Scheduler:
             # Prefix cache: the hit blocks already hold the KV of [0, hit);
             # the sequence enters as a chunk continuation at `hit` and only
             # the fresh tokens are charged to the budget.
+            # A sequence that wants prompt logprobs takes no hit: cached
+            # positions would have no hidden state to score. It still
+            # publishes its own blocks below.
             hit_blocks = (
-                self.allocator.lookup(seq.token_ids) if self.prefix_caching else []
+                self.allocator.lookup(seq.token_ids)
+                if self.prefix_caching and seq.prompt_logprobs is None else []
             )
             hit = len(hit_blocks) * bs
             end = min(n, hit + budget)

@@ -676,6 +676,46 @@ def token_logprobs(
     return out
 
 
+def lm_head_logprobs_supported(hidden: torch.Tensor, w: torch.Tensor) -> bool:
+    """Whether the fused HIP kernel can take (hidden [T, K], w [V, K]): bf16
+    on the GPU, K a multiple of 64, and skinny_gemm's staging rules (16-byte
+    aligned base, unit inner stride, row stride a multiple of 8 elements)."""
+    return (hidden.is_cuda and hidden.dtype == torch.bfloat16
+            and w.dtype == torch.bfloat16 and hidden.dim() == 2 and w.dim() == 2
+            and hidden.size(0) > 0 and hidden.size(1) == w.size(1)
+            and hidden.size(1) % 64 == 0
+            and _skg_stageable(hidden) and _skg_stageable(w) and has_hip_ext())
+
+
+def lm_head_logprobs(
+    hidden: torch.Tensor,   # [T, K] final-norm hidden states
+    w: torch.Tensor,        # [V, K] lm_head, or the tied embedding
+    rows: torch.Tensor,     # [R] int rows of hidden to score
+    targets: torch.Tensor,  # [R] int token id in [0, V) per scored row
+    softcap: float = 0.0,
+    nsplit: int = 0,        # vocabulary slices per 256-row tile, 0 = auto
+    block_rows: int = 1024,
+) -> torch.Tensor:
+    """lp [R] fp32 of torch_ref.lm_head_logprobs: the log-probability of
+    targets[r] given hidden[rows[r]], for prompt logprobs. On the GPU one
+    fused kernel: the lm_head GEMM with an epilogue that reduces every
+    vocabulary tile to a running log-sum-exp per row and picks the target
+    logit, so no logit is stored (workspace: (2 nsplit + 1) R floats).
+    Outside the kernel's envelope (CPU, fp16/fp32, odd K) and with
+    LLMQ_FUSED_PROMPT_LOGPROBS=0 the blocked composition runs instead: the
+    lm_head GEMM and token_logprobs over block_rows rows at a time."""
+    fused = os.environ.get("LLMQ_FUSED_PROMPT_LOGPROBS", "1") not in ("0", "false", "")
+    if not (fused and lm_head_logprobs_supported(hidden, w)):
+        return torch_ref.lm_head_logprobs(
+            hidden, w, rows, targets, softcap, block_rows,
+            token_logprobs_fn=token_logprobs)
+    lp = torch.empty(rows.numel(), dtype=torch.float32, device=hidden.device)
+    _EXT.lm_head_logprobs(
+        lp, hidden, w, rows.to(torch.int32).contiguous(),
+        targets.to(torch.int32).contiguous(), softcap, nsplit)
+    return lp
+
+
 def sample_tokens(
     logits: torch.Tensor,
     temperatures: torch.Tensor,

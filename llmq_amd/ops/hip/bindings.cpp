@@ -1305,6 +1305,69 @@ void token_logprobs(at::Tensor lp_out, at::Tensor ids_out, at::Tensor rank_out,
   });
 }
 
+// ------------------------------------------- prompt logprobs (lm_head) --
+
+// lp[r] = log_softmax(softcap(bf16(hidden[rows[r]] @ w^T)))[targets[r]]
+// without storing the logits (lm_head_logprobs.hip). nsplit: vocabulary
+// slices per M tile, 0 = auto. Workspace: (2 * nsplit + 1) * R floats.
+void lm_head_logprobs(at::Tensor lp, at::Tensor hidden, at::Tensor w,
+                      at::Tensor rows, at::Tensor targets, double softcap,
+                      long nsplit) {
+  CHECK_GPU(lp);
+  CHECK_GPU(hidden);
+  CHECK_GPU(w);
+  CHECK_GPU(rows);
+  CHECK_GPU(targets);
+  TORCH_CHECK(hidden.dim() == 2 && w.dim() == 2);
+  CHECK_LASTDIM(hidden);
+  CHECK_LASTDIM(w);
+  TORCH_CHECK(hidden.scalar_type() == at::kBFloat16 &&
+                  w.scalar_type() == at::kBFloat16,
+              "lm_head_logprobs: hidden and w must be bf16");
+  const int T = hidden.size(0), K = hidden.size(1), V = w.size(0);
+  const long R = rows.numel();
+  TORCH_CHECK(w.size(1) == K && T > 0 && V > 0 && K > 0);
+  TORCH_CHECK(K % SKG_BK == 0, "K must be a multiple of 64");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(hidden.data_ptr()) % 16 == 0 &&
+                  reinterpret_cast<uintptr_t>(w.data_ptr()) % 16 == 0,
+              "hidden and w must be 16-byte aligned");
+  TORCH_CHECK(hidden.stride(0) % 8 == 0 && w.stride(0) % 8 == 0,
+              "hidden and w row strides must be multiples of 8 elements");
+  TORCH_CHECK(rows.scalar_type() == at::kInt && rows.is_contiguous() &&
+                  targets.scalar_type() == at::kInt &&
+                  targets.is_contiguous() && targets.numel() == R,
+              "rows and targets must be contiguous int32 of equal length");
+  TORCH_CHECK(lp.scalar_type() == at::kFloat && lp.is_contiguous() &&
+                  lp.numel() == R,
+              "lp must be contiguous fp32 [R]");
+  TORCH_CHECK(nsplit >= 0 && nsplit <= 1024,
+              "nsplit must be in [0, 1024] (0 = auto)");
+  if (R == 0) return;
+  const int mt = (R + SKG_BM - 1) / SKG_BM;
+  const int ntiles = (V + SKG_BN - 1) / SKG_BN;
+  int z = (int)nsplit;
+  if (z <= 0) {
+    // auto: with few M tiles, enough slices to put a workgroup on each of
+    // the 256 CUs; with many, few slices, so that the M tiles running at
+    // the same time walk the same W tiles and share them through L2.
+    z = std::max(1, std::min(ntiles, 256 / mt));
+  }
+  at::Tensor ws = at::empty({2 * z + 1, R}, lp.options());
+  float* ws_m = ws.data_ptr<float>();
+  float* ws_s = ws_m + (long)z * R;
+  float* tgt = ws_s + (long)z * R;
+  hipLaunchKernelGGL(
+      lm_head_logprobs_kernel, dim3(mt, z), dim3(SKG_NT), 0, stream(), ws_m,
+      ws_s, tgt, reinterpret_cast<const __hip_bfloat16*>(hidden.data_ptr()),
+      reinterpret_cast<const __hip_bfloat16*>(w.data_ptr()),
+      rows.data_ptr<int>(), targets.data_ptr<int>(), (int)R, T, V, K,
+      (long)hidden.stride(0), (long)w.stride(0), (float)softcap,
+      softcap_reciprocal(softcap));
+  hipLaunchKernelGGL(lm_head_logprobs_merge_kernel, dim3((R + 255) / 256),
+                     dim3(256), 0, stream(), lp.data_ptr<float>(), ws_m, ws_s,
+                     tgt, z, (int)R);
+}
+
 }  // namespace
 
 TORCH_LIBRARY(llmq_amd, m) {
@@ -1321,6 +1384,7 @@ TORCH_LIBRARY(llmq_amd, m) {
   m.def("sample_gumbel_argmax(Tensor(a!) out, Tensor(b!) keys, Tensor logits, Tensor temps, Tensor req_seeds, Tensor req_pos, int seed, int step, Tensor? bounds=None, float softcap=0.0, Tensor? pen_table=None, Tensor? pen_slots=None, Tensor? pen_params=None) -> ()");
   m.def("topk_topp_bound(Tensor(a!) out_bound, Tensor logits, Tensor temps, Tensor top_ps, Tensor top_ks, float softcap=0.0, Tensor? min_ps=None, Tensor? pen_table=None, Tensor? pen_slots=None, Tensor? pen_params=None) -> ()");
   m.def("penalty_count_tokens(Tensor(a!) table, Tensor slots, Tensor tokens) -> ()");
+  m.def("lm_head_logprobs(Tensor(a!) lp, Tensor hidden, Tensor w, Tensor rows, Tensor targets, float softcap=0.0, int nsplit=0) -> ()");
   m.def("skinny_gemm(Tensor(a!) out, Tensor x, Tensor w, Tensor? bias, int splitk) -> ()");
   m.def("mxfp4_gemm(Tensor(a!) out, Tensor a_q, Tensor a_scale, Tensor w_codes, Tensor w_scales, Tensor? bias, int splitk) -> ()");
   m.def("quant_fp8_rows(Tensor(a!) q, Tensor(b!) scale, Tensor x) -> ()");
@@ -1349,6 +1413,7 @@ TORCH_LIBRARY_IMPL(llmq_amd, CUDA, m) {
   m.impl("topk_topp_bound", &topk_topp_bound);
   m.impl("penalty_count_tokens", &penalty_count_tokens);
   m.impl("token_logprobs", &token_logprobs);
+  m.impl("lm_head_logprobs", &lm_head_logprobs);
   m.impl("skinny_gemm", &skinny_gemm);
   m.impl("mxfp4_gemm", &mxfp4_gemm);
   m.impl("norm_add_norm", &norm_add_norm);

@@ -9,4 +9,5 @@
 #include "skinny_gemm.hip"
 #include "mxfp4_gemm.hip"
 #include "sampling.hip"
+#include "lm_head_logprobs.hip"
 #include "bindings.cpp"

@@ -498,6 +498,29 @@ def token_logprobs(
     return ids.to(torch.int32), lp, rank.to(torch.int32)
 
 
+def lm_head_logprobs(
+    hidden: torch.Tensor,   # [T, K] final-norm hidden states
+    w: torch.Tensor,        # [V, K] lm_head (or tied embedding)
+    rows: torch.Tensor,     # [R] int: rows of hidden to score
+    targets: torch.Tensor,  # [R] int: token id in [0, V) per scored row
+    softcap: float = 0.0,
+    block_rows: int = 1024,
+    token_logprobs_fn=None,  # ops passes its kernel-backed token_logprobs
+) -> torch.Tensor:
+    """lp [R] fp32: log-probability of targets[r] under log_softmax of the
+    soft-capped lm_head logits of hidden[rows[r]], the logits taken in the
+    model dtype as the lm_head GEMM stores them (token_logprobs' contract, so
+    a prompt token is scored by the same function as a sampled one). Blocked:
+    at most block_rows x V logits exist at a time, however long the prompt."""
+    fn = token_logprobs_fn or token_logprobs
+    rows, targets = rows.long(), targets.long()
+    out = torch.empty(rows.numel(), dtype=torch.float32, device=hidden.device)
+    for i in range(0, rows.numel(), block_rows):
+        logits = torch.nn.functional.linear(hidden[rows[i:i + block_rows]], w)
+        out[i:i + block_rows] = fn(logits, targets[i:i + block_rows], 0, softcap)[1][:, 0]
+    return out
+
+
 def sample_tokens(
     logits: torch.Tensor,  # [B, vocab] float
     temperatures: torch.Tensor,  # [B]

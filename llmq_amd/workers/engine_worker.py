@@ -58,6 +58,8 @@ class _FinishedRequest:
     cached_tokens: int = 0
     logprobs: Optional[List[Dict[str, Any]]] = None
     cumulative_logprob: Optional[float] = None
+    prompt_logprobs: Optional[List[Dict[str, Any]]] = None
+    prompt_cumulative_logprob: Optional[float] = None
 
 
 def format_logprobs(entries: List[tuple], tokenizer: Any) -> List[Dict[str, Any]]:
@@ -79,6 +81,16 @@ def format_logprobs(entries: List[tuple], tokenizer: Any) -> List[Dict[str, Any]
             ],
         }
         for tid, lp, rank, top in entries
+    ]
+
+
+def format_prompt_logprobs(entries: List[tuple], tokenizer: Any) -> List[Dict[str, Any]]:
+    """The engine's (token_id, logprob | None) per prompt token as the
+    Result's list of dicts."""
+    return [
+        {"token_id": tid, "logprob": lp,
+         "token": tokenizer.decode([tid], skip_special_tokens=False)}
+        for tid, lp in entries
     ]
 
 
@@ -221,6 +233,7 @@ class AsyncEngineBridge:
                     if out.finished:
                         # token strings: decoded here, once per request
                         entries = getattr(out, "logprobs", None)
+                        prompt_lp = getattr(out, "prompt_logprobs", None)
                         self._resolve(
                             out.request_id,
                             _FinishedRequest(
@@ -237,6 +250,10 @@ class AsyncEngineBridge:
                                 format_logprobs(entries, engine.tokenizer),
                                 cumulative_logprob=getattr(
                                     out, "cumulative_logprob", None),
+                                prompt_logprobs=None if prompt_lp is None else
+                                format_prompt_logprobs(prompt_lp, engine.tokenizer),
+                                prompt_cumulative_logprob=None if prompt_lp is None
+                                else float(sum(lp for _t, lp in prompt_lp[1:])),
                             ),
                         )
         except BaseException as exc:  # noqa: BLE001 — engine died: fail fast
@@ -478,6 +495,7 @@ class EngineWorker(BaseWorker):
                 pick(job.frequency_penalty, "frequency_penalty", 0.0)),
             min_p=float(pick(job.min_p, "min_p", 0.0)),
             logprobs=None if lp is None else int(lp),
+            prompt_logprobs=bool(pick(job.prompt_logprobs, "prompt_logprobs", False)),
         )
 
     def _format_prompt(self, job: Job) -> str:
@@ -522,4 +540,7 @@ class EngineWorker(BaseWorker):
             result.decode_ms = stats.decode_ms
             result.logprobs = getattr(stats, "logprobs", None)
             result.cumulative_logprob = getattr(stats, "cumulative_logprob", None)
+            result.prompt_logprobs = getattr(stats, "prompt_logprobs", None)
+            result.prompt_cumulative_logprob = getattr(
+                stats, "prompt_cumulative_logprob", None)
         return result
