@@ -3,7 +3,7 @@
 from __future__ import annotations
 
 from dataclasses import dataclass, field
-from typing import Optional
+from typing import Dict, Optional
 
 import torch
 
@@ -45,9 +45,26 @@ class EngineConfig:
     # through the scaled-MFMA GEMM; projections outside that kernel's
     # envelope stay fp8. Opt-in.
     quantization: str = "none"
+    # Multi-LoRA: adapter name -> PEFT directory (adapter_config.json +
+    # adapter_model.safetensors). All adapters stay resident; a request picks
+    # one with SamplingParams.lora. Ranks up to max_lora_rank. Not with
+    # quantization or tensor parallelism, and on the CPU path only: there are
+    # no HIP kernels for it yet, and a GPU engine refuses the setting.
+    lora_adapters: Dict[str, str] = field(default_factory=dict)
+    max_lora_rank: int = 64
 
     def __post_init__(self) -> None:
         self._check_quantization()
+        if self.lora_adapters:
+            if self.quantization != "none":
+                raise ValueError(
+                    "lora_adapters cannot be combined with quantization="
+                    f"{self.quantization!r} (adapters need unquantised projections)")
+            if self.tensor_parallel_size > 1:
+                raise ValueError(
+                    "lora_adapters cannot be combined with tensor_parallel_size > 1")
+            if not 1 <= self.max_lora_rank <= 64:
+                raise ValueError("max_lora_rank must be in [1, 64]")
         if self.shared_prefix_decode and not self.enable_prefix_caching:
             raise ValueError("shared_prefix_decode requires enable_prefix_caching")
 

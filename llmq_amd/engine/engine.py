@@ -114,6 +114,12 @@ class LLMEngine:
             ops._use_hip(torch.empty(1, device=self.device))
         if self.device.type == "cuda":
             _enable_tuned_gemms()
+        if config.lora_adapters and (self.device.type == "cuda" or tp > 1):
+            # before any weight is loaded. No quiet eager fall-back on the GPU:
+            # the adapter math needs HIP kernels, which do not exist yet
+            raise ValueError(
+                "lora_adapters run on the single-process CPU path only: there "
+                "are no HIP kernels for per-token adapters yet")
         self.max_model_len = min(
             config.max_model_len or self.spec.max_position_embeddings,
             self.spec.max_position_embeddings,
@@ -128,6 +134,10 @@ class LLMEngine:
             quantization=config.resolve_quantization(self.device),
         )
         self._load_or_init_weights()
+        if config.lora_adapters:
+            from llmq_amd.engine.lora import load_lora_adapters
+
+            load_lora_adapters(self.model, config.lora_adapters, config.max_lora_rank)
         self.tokenizer = load_tokenizer(
             config.model, self.spec.vocab_size, self.spec.bos_token_id, self.spec.eos_token_id
         )
@@ -291,6 +301,10 @@ class LLMEngine:
         if request_id in self._seqs:
             raise ValueError(f"duplicate request_id {request_id}")
         params = params or SamplingParams()
+        if params.lora is not None and params.lora not in self.config.lora_adapters:
+            raise ValueError(
+                f"request {request_id}: unknown LoRA adapter {params.lora!r} "
+                f"(loaded: {sorted(self.config.lora_adapters) or 'none'})")
         if params.logprobs is not None and params.logprobs > self.spec.vocab_size:
             params = replace(params, logprobs=self.spec.vocab_size)
         if prompt_token_ids is None:

@@ -5,6 +5,8 @@ from __future__ import annotations
 from dataclasses import dataclass
 import torch
 
+from llmq_amd.ops import LoraMeta
+
 
 @dataclass
 class TorchGatherIndices:
@@ -39,6 +41,7 @@ class PrefillMeta:
     max_seqlen: int
     slot_mapping: torch.Tensor  # [T] int64 global KV slots
     gather: "ChunkGather | None" = None  # set when any entry is a chunk
+    lora: "LoraMeta | None" = None  # rows that carry a LoRA adapter
 
     is_prefill: bool = True
     is_mixed: bool = False
@@ -57,6 +60,7 @@ class DecodeMeta:
     # follows them (each row's own blocks, >= 1 token).
     prefix_table: "torch.Tensor | None" = None  # [Wp] int32
     prefix_len: "torch.Tensor | None" = None    # [1] int32, on the device
+    lora: "LoraMeta | None" = None  # rows that carry a LoRA adapter
 
     is_prefill: bool = False
     is_mixed: bool = False
@@ -73,6 +77,7 @@ class MixedMeta:
     decode: "DecodeMeta"
     prefill: "PrefillMeta"
     slot_mapping: torch.Tensor  # [T] both segments, in row order
+    lora: "LoraMeta | None" = None  # over the packed rows of both segments
 
     is_prefill: bool = False
     is_mixed: bool = True

@@ -170,13 +170,16 @@ class PrefixCachingAllocator:
     def refcount(self, block: int) -> int:
         return self._ref[block]
 
-    def lookup(self, token_ids: List[int]) -> List[int]:
+    def lookup(self, token_ids: List[int], root=_ROOT) -> List[int]:
         """Longest chain of cached blocks matching the head of ``token_ids``;
         takes a reference on each. Capped at ((n - 1) // block_size) blocks so
-        at least one prompt token is always computed and sampled from."""
+        at least one prompt token is always computed and sampled from.
+        `root` names the tree: K/V depend on the LoRA adapter, so each
+        adapter name is a root of its own (node ids are ints, names are
+        strings: the trees cannot meet)."""
         bs = self.block_size
         hit: List[int] = []
-        parent = self._ROOT
+        parent = root
         for i in range((len(token_ids) - 1) // bs):
             block = self._cache.get((parent, tuple(token_ids[i * bs:(i + 1) * bs])))
             if block is None:
@@ -190,12 +193,12 @@ class PrefixCachingAllocator:
         return hit
 
     def register(self, seq_tokens: List[int], block_table: List[int],
-                 upto_tokens: int) -> None:
+                 upto_tokens: int, root=_ROOT) -> None:
         """Enter the full blocks covering [0, upto_tokens) into the cache.
         Idempotent. A block whose content is already cached under another id
         stays unregistered (the chain continues under the cached one)."""
         bs = self.block_size
-        parent = self._ROOT
+        parent = root
         for i in range(upto_tokens // bs):
             block = block_table[i]
             node = self._node_of.get(block)

@@ -113,8 +113,32 @@ class ModelRunner:
         self.paged_gather = os.environ.get(
             "LLMQ_PAGED_GATHER", "1") not in ("0", "false", "")
         self.shared_prefix = self._shared_prefix_active()
+        # Multi-LoRA: adapter name -> row of the stacks (model.lora)
+        self.lora_index: Dict[str, int] = (
+            {name: i for i, name in enumerate(config.lora_adapters)}
+            if model.lora is not None else {})
         if self.use_graphs:
             self._alloc_static_buffers()
+
+    # -- multi-LoRA row metadata -------------------------------------------
+
+    def _lora_rows(self, seqs: List[Sequence], counts: Optional[List[int]] = None) -> List[int]:
+        """Adapter index per packed row (-1 = base model): seqs[i] holds
+        counts[i] rows (default one each)."""
+        idx = self.lora_index
+        per_seq = [idx[s.lora] if s.lora is not None else -1 for s in seqs]
+        if counts is None:
+            return per_seq
+        return [a for a, n in zip(per_seq, counts) for _ in range(n)]
+
+    def _lora_meta(self, row_adapter: List[int]) -> Optional[ops.LoraMeta]:
+        """ops.LoraMeta of a step; None when no row carries an adapter (the
+        forward then runs what it ran before)."""
+        if not self.lora_index or max(row_adapter, default=-1) < 0:
+            return None
+        arrays = ops.lora_meta_arrays(row_adapter, len(self.lora_index))
+        packed = torch.from_numpy(np.concatenate(arrays)).to(self.device)
+        return ops.LoraMeta(*packed.split([a.size for a in arrays]))
 
     # -- shared-prefix decode ---------------------------------------------
 
@@ -323,6 +347,8 @@ class ModelRunner:
         ids, pos, slot_mapping, meta, rel_last = self._build_prefill_meta(
             seqs, chunks, dev
         )
+        meta.lora = self._lora_meta(
+            self._lora_rows(seqs, [e - st for st, e in chunks]))
         input_ids = torch.tensor(ids, dtype=torch.long, device=dev)
         positions = torch.tensor(pos, dtype=torch.long, device=dev)
         hidden = self.model.forward(input_ids, positions, self.kv_cache, meta)
@@ -427,6 +453,9 @@ class ModelRunner:
             ),
             prefill=pmeta,
             slot_mapping=slot_mapping,
+            lora=self._lora_meta(
+                self._lora_rows(dseqs)
+                + self._lora_rows(pseqs, [e - st for st, e in chunks])),
         )
         input_ids = torch.tensor(ids, dtype=torch.long, device=dev)
         positions = torch.tensor(pos, dtype=torch.long, device=dev)
@@ -471,6 +500,7 @@ class ModelRunner:
             context_lens=torch.tensor(
                 [c - P * bs for c in ctx], dtype=torch.int32, device=dev),
             slot_mapping=torch.tensor(slots, dtype=torch.long, device=dev),
+            lora=self._lora_meta(self._lora_rows(seqs)),
         )
         if self.shared_prefix:
             meta.prefix_table = torch.tensor(

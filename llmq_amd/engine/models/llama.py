@@ -131,6 +131,9 @@ class CausalLM:
         self.layers: List[LayerWeights] = []
         self.final_norm: Optional[torch.Tensor] = None
         self.lm_head: Optional[torch.Tensor] = None
+        # Multi-LoRA (engine/lora.py): per layer {projection: ops.LoraStacks},
+        # None without adapters
+        self.lora: Optional[List[Dict[str, ops.LoraStacks]]] = None
         self.rope_cache = ops.build_rope_cache(
             spec.max_position_embeddings, spec.head_dim, spec.rope_theta, device,
             rope_scaling=spec.rope_scaling,
@@ -315,6 +318,10 @@ class CausalLM:
             return ops.fp8_linear(h[0], h[1], w, scale, bias)
         return _proj(h, w, bias)
 
+    def _lora(self, out: torch.Tensor, x, layer: int, name: str, lmeta) -> torch.Tensor:
+        """The step's adapters on top of projection `name`, in place."""
+        return ops.lora_apply(out, x, self.lora[layer][name], lmeta)
+
     def _add_norm(self, x, residual, w_post, w, quant: bool):
         """residual += x (Gemma-2: += norm(x, w_post)); h = norm(residual, w).
         Returns (h, residual), h quantised when `quant`."""
@@ -387,10 +394,14 @@ class CausalLM:
         else:
             h = self._norm(x, self.layers[0].input_norm)
         n_layers = len(self.layers)
+        # rows that carry a LoRA adapter this step (None: no launch added)
+        lmeta = meta.lora if self.lora is not None else None
         for i, lw in enumerate(self.layers):
             # ---- attention block (h = normed input, set by the previous
             # block's fused norm — launch count is the decode-step bound)
             qkv = self._linear(h, lw, "qkv", lw.qkv_bias)
+            if lmeta is not None:
+                self._lora(qkv, h, i, "qkv", lmeta)
             q, k, v = qkv.split([self.q_size, self.kv_size, self.kv_size], dim=-1)
             T = q.shape[0]
             q = q.view(T, self.heads, s.head_dim)
@@ -436,6 +447,8 @@ class CausalLM:
             attn = attn.reshape(T, self.q_size)
             attn_out = self._linear(
                 ops.quant_fp8_rows(attn) if fp8 else attn, lw, "o")
+            if lmeta is not None:
+                self._lora(attn_out, attn, i, "o", lmeta)
             if tp is not None:
                 attn_out = tp.all_reduce(attn_out)
             # residual += attn_out (Gemma-2: its post norm); h = norm(residual)
@@ -443,12 +456,16 @@ class CausalLM:
                 attn_out, residual, lw.post_attn_norm, lw.pre_mlp_norm, fp8)
             # ---- MLP block
             gate_up = self._linear(h, lw, "gate_up")
+            if lmeta is not None:
+                self._lora(gate_up, h, i, "gate_up", lmeta)
             if fp8:
                 act = (ops.gelu_tanh_and_mul_quant_fp8(gate_up) if s.gelu
                        else ops.silu_and_mul_quant_fp8(gate_up))
             else:
                 act = ops.gelu_tanh_and_mul(gate_up) if s.gelu else ops.silu_and_mul(gate_up)
             mlp_out = self._linear(act, lw, "down")
+            if lmeta is not None:
+                self._lora(mlp_out, act, i, "down", lmeta)
             if tp is not None:
                 mlp_out = tp.all_reduce(mlp_out)
             # The next block's input norm (or the final norm) fuses with this

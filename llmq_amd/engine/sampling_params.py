@@ -41,6 +41,9 @@ class SamplingParams:
     # Such a request reads nothing from the prefix cache: every position needs
     # its hidden state.
     prompt_logprobs: bool = False
+    # Name of one of EngineConfig.lora_adapters to generate with (None = the
+    # base model). The engine rejects a name it was not started with.
+    lora: Optional[str] = None
 
     def __post_init__(self) -> None:
         if self.temperature < 0:

@@ -47,7 +47,7 @@ class Sequence:
         "request_id", "token_ids", "prompt_len", "params", "status",
         "block_table", "arrival_time", "first_token_time", "finish_reason",
         "output_text", "num_preemptions", "prefilled", "prefill_start_time",
-        "uid", "cached_tokens", "logprobs", "prompt_logprobs",
+        "uid", "cached_tokens", "logprobs", "prompt_logprobs", "lora",
     )
 
     def __init__(self, request_id: str, prompt_token_ids: List[int], params: SamplingParams,
@@ -61,6 +61,7 @@ class Sequence:
         self.token_ids: List[int] = list(prompt_token_ids)
         self.prompt_len = len(prompt_token_ids)
         self.params = params
+        self.lora: Optional[str] = params.lora  # adapter name, None = base
         self.status = SeqStatus.WAITING
         self.block_table: List[int] = []
         self.arrival_time = arrival_time
@@ -244,7 +245,7 @@ class Scheduler:
             # positions would have no hidden state to score. It still
             # publishes its own blocks below.
             hit_blocks = (
-                self.allocator.lookup(seq.token_ids)
+                self.allocator.lookup(seq.token_ids, self._root(seq))
                 if self.prefix_caching and seq.prompt_logprobs is None else []
             )
             hit = len(hit_blocks) * bs
@@ -302,7 +303,13 @@ class Scheduler:
         # segment into the cache (rope_and_cache / qknorm_rope_and_cache)
         # before that layer's attention gathers from it, all prefill work
         # runs on one stream, and step() joins the decode stream at its end.
-        self.allocator.register(seq.token_ids, seq.block_table, end)
+        self.allocator.register(
+            seq.token_ids, seq.block_table, end, self._root(seq))
+
+    def _root(self, seq: Sequence):
+        """The prefix tree of a sequence: its LoRA adapter's, or the base
+        model's. K/V differ between adapters, so no block crosses trees."""
+        return seq.lora if seq.lora is not None else self.allocator._ROOT
 
     def _release(self, seq: Sequence) -> None:
         if self.on_release is not None:

@@ -716,6 +716,31 @@ def lm_head_logprobs(
     return lp
 
 
+# ----------------------------------------------------------- multi-LoRA --
+# Per-token adapters on top of a layer projection. The data structures and
+# the numeric contract live in torch_ref. There is no HIP kernel for it yet,
+# and a GPU call raises: no GPU hot path runs eager PyTorch.
+
+LoraStacks = torch_ref.LoraStacks
+LoraMeta = torch_ref.LoraMeta
+lora_meta = torch_ref.lora_meta
+lora_meta_arrays = torch_ref.lora_meta_arrays
+
+
+def lora_apply(
+    out: torch.Tensor,     # [T, N] the projection's output, updated in place
+    x: torch.Tensor,       # [T, K] the projection's input
+    stacks: LoraStacks,
+    meta: LoraMeta,
+) -> torch.Tensor:
+    """torch_ref.lora_apply: out[t] += scale * B_a (A_a x[t]) for the rows t
+    that meta lists under an adapter a. CPU only."""
+    if x.is_cuda:
+        raise RuntimeError(
+            "lora_apply has no HIP kernel yet: LoRA adapters run on the CPU path only")
+    return torch_ref.lora_apply(out, x, stacks, meta)
+
+
 def sample_tokens(
     logits: torch.Tensor,
     temperatures: torch.Tensor,

@@ -563,3 +563,94 @@ def sample_tokens(
         probs = torch.softmax(l, dim=-1)
         out[i] = torch.multinomial(probs, 1, generator=generator).squeeze(0)
     return out
+
+
+# ------------------------------------------------------------ multi-LoRA --
+
+
+class LoraStacks:
+    """The resident adapters of one layer projection. The projection packs S
+    HF modules (`slices`: their (column start, width) in the output); module s
+    of adapter a is A[a, s*R:(s+1)*R] ([R, K]) and B[a, start_s:start_s +
+    width_s] ([width_s, R]). R is the largest loaded rank: smaller ranks,
+    modules an adapter does not target and output columns outside the slices
+    are zero."""
+
+    __slots__ = ("a", "b", "scale", "slices")
+
+    def __init__(self, a: torch.Tensor, b: torch.Tensor, scale: torch.Tensor,
+                 slices: Tuple[Tuple[int, int], ...]):
+        self.a = a          # [n_adapters, S*R, K]
+        self.b = b          # [n_adapters, N, R]
+        self.scale = scale  # [n_adapters] fp32
+        self.slices = tuple((int(s), int(w)) for s, w in slices)
+
+
+class LoraMeta:
+    """Which rows of a step carry which adapter: the rows grouped by adapter
+    into 16-row tiles. perm[tile*16 + i] is the row of tile row i (-1 = pad),
+    tile_adapter[tile] the tile's adapter, n_tiles[0] the tiles in use; rows
+    without an adapter appear nowhere. The arrays always have ceil(T/16) +
+    n_adapters tiles, the worst case for T rows. The tiled, fixed-size form
+    is kept on purpose although only the CPU reference reads it today: it is
+    the layout a 16-row MFMA kernel with a launch shape that depends on T
+    alone would read, and the one the tests pin down."""
+
+    __slots__ = ("perm", "tile_adapter", "n_tiles")
+
+    def __init__(self, perm: torch.Tensor, tile_adapter: torch.Tensor,
+                 n_tiles: torch.Tensor):
+        self.perm = perm                  # [tiles*16] int32
+        self.tile_adapter = tile_adapter  # [tiles] int32
+        self.n_tiles = n_tiles            # [1] int32
+
+
+def lora_meta_arrays(row_adapter, n_adapters: int):
+    """(perm, tile_adapter, n_tiles) numpy int32 arrays of LoraMeta for
+    row_adapter[t] = adapter of row t (-1 = none). O(T) host work."""
+    import numpy as np
+
+    ra = np.asarray(row_adapter, dtype=np.int64)
+    tiles = (len(ra) + 15) // 16 + n_adapters
+    perm = np.full(tiles * 16, -1, dtype=np.int32)
+    tile_adapter = np.zeros(tiles, dtype=np.int32)
+    rows = np.nonzero(ra >= 0)[0]
+    rows = rows[np.argsort(ra[rows], kind="stable")]
+    counts = np.bincount(ra[rows], minlength=n_adapters)
+    t = start = 0
+    for a in np.nonzero(counts)[0]:
+        c = int(counts[a])
+        perm[t * 16:t * 16 + c] = rows[start:start + c]
+        nt = (c + 15) // 16
+        tile_adapter[t:t + nt] = a
+        t += nt
+        start += c
+    return perm, tile_adapter, np.array([t], dtype=np.int32)
+
+
+def lora_meta(row_adapter, n_adapters: int, device="cpu") -> LoraMeta:
+    perm, tile_adapter, n_tiles = lora_meta_arrays(row_adapter, n_adapters)
+    return LoraMeta(*(torch.from_numpy(t).to(device)
+                      for t in (perm, tile_adapter, n_tiles)))
+
+
+def lora_apply(out: torch.Tensor, x: torch.Tensor, stacks: LoraStacks,
+               meta: LoraMeta) -> torch.Tensor:
+    """In place, for every row t that meta lists under adapter a:
+        h         = dtype(fp32 sum_k x[t, k] A[a, :, k])
+        out[t, n] = dtype(fp32(out[t, n]) + scale[a] * fp32 sum_j h[s R + j] B[a, n, j])
+    for n in slice s; other rows and columns keep their bits. `dtype` is the
+    tensors' own (bf16 on the GPU: h is rounded once, out once)."""
+    R = stacks.b.shape[2]
+    perm = meta.perm[: int(meta.n_tiles[0]) * 16].view(-1, 16).long()
+    adapters = meta.tile_adapter[: perm.shape[0]]
+    for a in adapters.unique().tolist():
+        rows = perm[adapters == a].reshape(-1)
+        rows = rows[rows >= 0]
+        h = (x[rows].float() @ stacks.a[a].float().t()).to(x.dtype).float()
+        for s, (start, width) in enumerate(stacks.slices):
+            cols = slice(start, start + width)
+            delta = h[:, s * R:(s + 1) * R] @ stacks.b[a, cols].float().t()
+            out[rows, cols] = (out[rows, cols].float()
+                               + stacks.scale[a].float() * delta).to(out.dtype)
+    return out

@@ -116,3 +116,57 @@ def build_tiny_checkpoint(
         "bos_token": "<s>", "eos_token": "</s>", "unk_token": "<unk>",
     }))
     return str(path)
+
+
+def build_tiny_lora_adapter(
+    path,
+    base,
+    rank: int = 8,
+    alpha: float = 16.0,
+    target_modules=("q_proj", "k_proj", "v_proj", "o_proj",
+                    "gate_proj", "up_proj", "down_proj"),
+    seed: int = 0,
+    std: float = 0.05,
+    use_rslora: bool = False,
+    **config_extra,
+) -> str:
+    """Write a random PEFT-layout LoRA adapter (adapter_config.json +
+    adapter_model.safetensors) for `base`, a tiny preset's name (e.g.
+    "tiny-llama") or a checkpoint directory; returns
+    path. Both A and B are random (a trained adapter's B is non-zero too), so
+    the adapter changes the model's output. `config_extra` overrides fields of
+    adapter_config.json."""
+    import torch
+    from safetensors.torch import save_file
+
+    path = Path(path)
+    path.mkdir(parents=True, exist_ok=True)
+    from llmq_amd.engine.model_specs import resolve_spec
+
+    spec = resolve_spec(str(base))  # a preset name or a checkpoint directory
+    hidden, inter = spec.hidden_size, spec.intermediate_size
+    q, kv = spec.num_heads * spec.head_dim, spec.num_kv_heads * spec.head_dim
+    shapes = {  # module -> (block, out features, in features)
+        "q_proj": ("self_attn", q, hidden), "k_proj": ("self_attn", kv, hidden),
+        "v_proj": ("self_attn", kv, hidden), "o_proj": ("self_attn", hidden, q),
+        "gate_proj": ("mlp", inter, hidden), "up_proj": ("mlp", inter, hidden),
+        "down_proj": ("mlp", hidden, inter),
+    }
+    gen = torch.Generator().manual_seed(seed)
+    tensors = {}
+    for i in range(spec.num_layers):
+        for module in target_modules:
+            if module not in shapes:  # e.g. lm_head: named in the config only
+                continue
+            block, n_out, n_in = shapes[module]
+            key = f"base_model.model.model.layers.{i}.{block}.{module}."
+            tensors[key + "lora_A.weight"] = torch.randn(rank, n_in, generator=gen) * std
+            tensors[key + "lora_B.weight"] = torch.randn(n_out, rank, generator=gen) * std
+    save_file(tensors, str(path / "adapter_model.safetensors"))
+    (path / "adapter_config.json").write_text(json.dumps({
+        "peft_type": "LORA", "r": rank, "lora_alpha": alpha,
+        "target_modules": list(target_modules), "bias": "none",
+        "use_dora": False, "use_rslora": use_rslora, "modules_to_save": None,
+        "rank_pattern": {}, "alpha_pattern": {}, **config_extra,
+    }, indent=1))
+    return str(path)
